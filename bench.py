@@ -2,7 +2,8 @@
 """Headline benchmark: codeword-decodes/sec, 5G LDPC BG1 n=8448 rate 1/3, BP 20 iterations
 (BASELINE.json metric, config C2; C3 = the same sharded over ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--cn-update minsum|boxplus-phi|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--cn-update minsum|boxplus-phi|...] [--full]
+                    [--dump-outputs DIR]
 
 One step = one pass of the decoder hot path over one resident batch: LDPC5GDecoder.call on a
 [B, 8448] float32 LLR tensor that is already in HBM (generated untimed by the library's own
@@ -10,6 +11,14 @@ chain: BinarySource -> LDPC5GEncoder -> 64-QAM Mapper -> AWGN -> app Demapper), 
 the error count against the transmitted bits and, for N > 1 ranks, the RCCL all-reduce of the
 four int64 counters (the only collective of the path; ranks are otherwise independent ->
 weak scaling, B codewords per GPU).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `ber`, `bler`,
+`roofline`).  `--full` adds the secondary measurements below that take runs of their own (`generic_kernel`,
+`end_to_end`, `sim_ber`, `also`, `cpu_baseline`, `extra`).  `--dump-outputs DIR` writes, after the timed steps, what the
+last timed step computed (rank 0) as float32 / float64 .npy files, at most 64 MB together:
+  decoded_bits_sample.npy   [R, 2816] the decoder's hard decisions for a fixed, seeded sample of R <= 4096 codewords
+  codeword_bit_errors.npy   [B] bit errors of each codeword of the batch against the transmitted bits
+  error_counters.npy        [4] bit errors, block errors, bits, blocks summed over the timed steps (and ranks)
 
 `roofline`     the dominant kernel keeps its messages on chip, so it is priced against the unit it loads, not
                against HBM: bound "valu", achieved = wave64 VALU instructions per second = (SQ_INSTS_VALU per
@@ -24,7 +33,7 @@ weak scaling, B codewords per GPU).  Rank 0 prints ONE JSON line.
 `cpu_baseline` oracle/ldpc_bp.c (plain-C restatement of the reference algorithm, OpenMP over codewords, all host
                cores) on a bounded sample of the same LLRs, rank 0, N=1 - for BOTH rules.
 `extra`        short runs of the secondary workloads (BASELINE configs C4 and C5) with their own roofline and
-               cpu_baseline, so that the driver's default invocation times them too (`--no-extra` skips).
+               cpu_baseline, so that `--full` times them too (`--no-extra` skips).
 """
 import argparse
 import hashlib
@@ -46,6 +55,7 @@ NUM_SIMD, CLOCK_GHZ, NUM_CU = 1024, 2.4, 256
 VALU_PEAK_GINST = NUM_SIMD * CLOCK_GHZ / 2.0          # wave64 VALU instructions per ns -> G inst/s (2 cycles each)
 LDS_PIPE_PEAK_GCYC = NUM_CU * CLOCK_GHZ               # LDS-pipeline cycles per ns: one LDS per CU
 COUNTERS = os.path.join(ROOT, "profiles", "counters.json")
+DUMP_LIMIT_BYTES, DUMP_ROWS, DUMP_SEED = 64 << 20, 4096, 20250923
 
 
 def b_msg(num_iter, k_out):
@@ -200,7 +210,7 @@ def ranks_seen(world, rank, device):
 
 def self_launch_argv(n_gpus, argv=None, port=None):
     """Command line that runs this file as N ranks of ONE node (one process per GPU, RCCL over xGMI) - exactly the
-    launch the driver uses for N > 1; `python bench.py --gpus N` from a plain shell re-executes itself as this."""
+    launch the driver uses for N > 1; `python bench.py --gpus N` from a plain shell runs this as its child."""
     import socket
     if port is None:
         with socket.socket() as s:
@@ -211,18 +221,20 @@ def self_launch_argv(n_gpus, argv=None, port=None):
 
 
 def self_launch(n_gpus):
-    """`bench.py --gpus N` without WORLD_SIZE: replace this process by the N-rank launch (rank 0 prints the ONE line)."""
+    """`bench.py --gpus N` without WORLD_SIZE: run the N-rank launch as a child process and exit with its status (rank 0
+    prints the ONE line)."""
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if os.environ.get("SAMD_BENCH_BACKEND", "nccl") == "nccl" and have < n_gpus and "--dry-dist" not in sys.argv:
         print(f"bench.py: --gpus {n_gpus} but only {have} GPU(s) visible (SAMD_BENCH_BACKEND=gloo shares devices "
               "between ranks for a code-path check)", file=sys.stderr)
         sys.exit(2)
+    import subprocess
     argv = self_launch_argv(n_gpus)
     sys.stdout.flush()
-    os.environ["SAMD_BENCH_CHILD"] = "1"    # the ranks must not launch again (e.g. a launcher that gave them WORLD_SIZE=1)
+    env = dict(os.environ, SAMD_BENCH_CHILD="1")   # the ranks must not launch again (e.g. a launcher that gave them WORLD_SIZE=1)
     for k_ in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        os.environ.pop(k_, None)
-    os.execv(sys.executable, argv)
+        env.pop(k_, None)
+    sys.exit(subprocess.call(argv, env=env))
 
 
 def timed_steps(step, steps, warmup, world, device, device_sync, counters=None):
@@ -256,6 +268,26 @@ def counted_step(decode, u, counters, count_into, world, events=None):
         if world > 1:                   # the path's only collective: 4 x int64 error counters (RCCL)
             reduce_sum(counters, world)
     return step
+
+
+def dump_sample_rows(batch, row_bytes, fixed_bytes):
+    """--dump-outputs: the sorted rows of the fixed, seeded sample (at most DUMP_ROWS, and what fits beside `fixed_bytes`)"""
+    rows = max(0, min(batch, DUMP_ROWS, (DUMP_LIMIT_BYTES - fixed_bytes) // max(row_bytes, 1)))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(batch, size=rows, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 or float64, at most DUMP_LIMIT_BYTES together"""
+    arrays = {name: np.ascontiguousarray(a) for name, a in arrays.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------ C4: OFDM 4x2 LMMSE
@@ -669,7 +701,16 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c2", "c4", "c5", "c5_bp"],
                     help="c2 = headline LDPC decode (default); c4 = OFDM 4x2 LMMSE pass; c5 = Polar SCL-8; c5_bp = Polar BP-20 "
                          "on the C5 code (single GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: also the secondary measurements (generic_kernel, end_to_end, sim_ber, also, cpu_baseline, extra); "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="c2: write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "c2" or args.dry_dist):
+        ap.error("--dump-outputs writes the headline (c2) workload's outputs")
     if args.workload == "c5_bp":
         return print(json.dumps(bench_c5_bp(args)))
     if args.workload == "c4":
@@ -722,12 +763,18 @@ def main():
     t_gen = time.perf_counter() - t0
     counters = torch.zeros(4, dtype=torch.int64, device=dev)
 
-    def run(dec, steps, warmup):
+    def run(dec, steps, warmup, keep=None):
         # untimed preparation, independent of --warmup: the first decode of a handle generates and compiles its kernel (hipRTC,
         # ~4 s of host time during which the GPU idles and drops its clocks); two more decodes bring the clocks back.  With
         # --warmup 1 and this missing, the timed steps measured the clock ramp (20.4 instead of 16.1 ms per step, profiles/r05smoke)
+        # keep: a dict that receives each step's decisions as "u_hat" (--dump-outputs reads the last timed step's)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-        step = counted_step(lambda: dec(llr), u, counters, phy.utils.metrics.count_errors_into, world, ev)
+
+        def decode_kept():
+            keep["u_hat"] = dec(llr)
+            return keep["u_hat"]
+        step = counted_step((lambda: dec(llr)) if keep is None else decode_kept, u, counters, phy.utils.metrics.count_errors_into,
+                            world, ev)
         for _ in range(3):
             step(None)                      # (the counters are zeroed again before the timed region)
         torch.cuda.synchronize()
@@ -742,7 +789,16 @@ def main():
             return False
 
     dec = make_dec(args.cn_update)
-    t_wall, dec_ms, c = run(dec, args.steps, args.warmup)
+    last = {} if args.dump_outputs else None
+    t_wall, dec_ms, c = run(dec, args.steps, args.warmup, last)
+    if last is not None and rank == 0:
+        u_hat = last.pop("u_hat").as_subclass(torch.Tensor)
+        rows = dump_sample_rows(B, 4 * k, 4 * B + 8 * 4)
+        dump_outputs(args.dump_outputs, {
+            "decoded_bits_sample": u_hat[torch.from_numpy(rows).to(u_hat.device)].to(torch.float32).cpu().numpy(),
+            "codeword_bit_errors": (u_hat != u).sum(dim=1).to(torch.float32).cpu().numpy(),
+            "error_counters": np.asarray(c, dtype=np.float64)})
+        del u_hat
     onchip = bool(dec._onchip_ok)
     jit_ran = onchip and args.cn_update in ("minsum", "offset-minsum") and specialised_ran(dec)
     value = B * world * args.steps / t_wall
@@ -761,7 +817,7 @@ def main():
         "roofline": c2_roofline(args.cn_update, onchip, B, k, args.num_iter, dec_ms, jit_ran),
     }
 
-    if jit_ran:
+    if args.full and jit_ran:
         # the same decode on the GENERIC on-chip kernel (the lists walked by scalar code, ldpc5g_decode_msg_kernel) in the same
         # run: what the specialisation buys, and that both produce the same decisions
         with _ffi.option("SAMD_LDPC_JIT", "0"):
@@ -780,18 +836,19 @@ def main():
         ub = src([B, k])
         ll = demap(awgn(mapper(enc(ub)), no), no)
         phy.utils.metrics.count_errors_into(ub, dec(ll), counters[:2])
-    chain_step()
-    barrier(world, torch.cuda.synchronize)
-    t0 = time.perf_counter()
-    n_e2e = 3
-    for _ in range(n_e2e):
+    if args.full:
         chain_step()
-    barrier(world, torch.cuda.synchronize)
-    t_e2e = (time.perf_counter() - t0) / n_e2e
-    out["end_to_end"] = {"codewords_per_s_per_gpu": round(B / t_e2e, 1), "ms_per_batch": round(t_e2e * 1e3, 2),
-                         "stages": "BinarySource, LDPC5GEncoder, Mapper, AWGN, Demapper(app), LDPC5GDecoder, count_errors"}
+        barrier(world, torch.cuda.synchronize)
+        t0 = time.perf_counter()
+        n_e2e = 3
+        for _ in range(n_e2e):
+            chain_step()
+        barrier(world, torch.cuda.synchronize)
+        t_e2e = (time.perf_counter() - t0) / n_e2e
+        out["end_to_end"] = {"codewords_per_s_per_gpu": round(B / t_e2e, 1), "ms_per_batch": round(t_e2e * 1e3, 2),
+                             "stages": "BinarySource, LDPC5GEncoder, Mapper, AWGN, Demapper(app), LDPC5GDecoder, count_errors"}
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # The Monte-Carlo driver itself (north_star's use case; reference utils/misc.py:694-784): the same chain as mc_fun of
         # sim_ber over three Eb/N0 points.  With num_target_block_errors the driver must read the counters after EVERY iteration
         # (one device synchronisation - and, for N > 1, one all-reduce of 4 x int64 - per iteration), exactly where the reference
@@ -835,7 +892,8 @@ def main():
                           **sims}
 
     dec2 = None
-    if args.also and args.also != "none" and args.also != args.cn_update:
+    also = args.full and args.also and args.also != "none"
+    if also and args.also != args.cn_update:
         dec2 = make_dec(args.also)
         steps2 = max(2, args.steps // 3)
         n_before = int(_ffi.lib().samd_ldpc5g_jit_launches(enc._handle(dec2._nb_pruned_nodes)))
@@ -861,7 +919,7 @@ def main():
                                                 "are not bit-identical to the oracle (tests keep the round-2 tolerance bars)"}
             del dec3
 
-    if args.also and args.also != "none":
+    if also:
         # cn_schedule="layered" (one sub-iteration per base row), half the iterations, on its own
         # on-chip engine (csrc/ldpc5g_onchip_ly.hip); same batch, same rule as the headline
         decl = phy.fec.ldpc.LDPC5GDecoder(enc, cn_update=args.cn_update, cn_schedule="layered", num_iter=max(1, args.num_iter // 2),
@@ -876,7 +934,7 @@ def main():
             "ms_per_step": round(tl / stepsl * 1e3, 3), "ber": float(cl[0] / max(cl[2], 1)), "bler": float(cl[1] / max(cl[3], 1))}
         del decl
 
-    if args.also and args.also != "none" and world == 1:
+    if also and world == 1:
         # return_state / msg_v2c (the iterative detection-and-decoding use): the same 20 iterations as four calls
         # of five with the decoder state handed from call to call; a quarter of the batch (an image and its deferred tensor per call)
         Bs = max(1024, B // 4)
@@ -914,14 +972,14 @@ def main():
             "hbm_resident_engine": {"value": round(Bs / th, 1), "unit": "codewords/s", "ms_per_call": round(th / 4 * 1e3, 3)}}
         del decs, llrs
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c2(llr, k, n, m, args.cn_update, args.num_iter, dec, 12.0, B)
         out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
         if dec2 is not None:
             out["also"]["cpu_baseline"] = cpu_baseline_c2(llr, k, n, m, args.also, args.num_iter, dec2, 8.0, B)
             out["also"]["speedup_vs_cpu_baseline"] = round(out["also"]["value"] / out["also"]["cpu_baseline"]["value"], 1)
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         del llr, u
         torch.cuda.empty_cache()
         out["extra"] = {}

@@ -119,3 +119,36 @@ def test_bench_self_launch_command_line():
     argv = bench.self_launch_argv(8, ["--gpus", "8", "--steps", "3"], port=29511)
     assert argv[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=8" in argv
     assert argv[argv.index("--master-addr") + 1] == "127.0.0.1" and argv[-4:] == ["--gpus", "8", "--steps", "3"]
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: the same sorted, distinct rows in every run, and never more bytes than the limit"""
+    sys.path.insert(0, ROOT)
+    import bench
+    a, b = bench.dump_sample_rows(65536, 4 * 2816, 4 * 65536 + 32), bench.dump_sample_rows(65536, 4 * 2816, 4 * 65536 + 32)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_ROWS
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 65536
+    assert len(bench.dump_sample_rows(100, 4 * 2816, 0)) == 100
+    big = bench.dump_sample_rows(10 ** 6, 4 * 8448, 4 * 10 ** 6)
+    assert len(big) * 4 * 8448 + 4 * 10 ** 6 <= bench.DUMP_LIMIT_BYTES
+
+
+def test_dump_outputs_writes_float_arrays_only(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), {"x": np.arange(6, dtype=np.float32).reshape(2, 3), "c": np.array([1.0, 2.0])})
+    assert np.array_equal(np.load(out / "x.npy"), np.arange(6, dtype=np.float32).reshape(2, 3))
+    assert np.load(out / "c.npy").dtype == np.float64
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(out), {"i": np.arange(3)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(out), {"big": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+
+
+def test_bench_rejects_dump_outputs_off_the_headline(tmp_path):
+    """--dump-outputs belongs to the c2 workload; --steps below 1 is refused (both before any GPU work)"""
+    import subprocess
+    for extra in (["--workload", "c4", "--dump-outputs", str(tmp_path)], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode == 2 and "error" in r.stderr, (extra, r.stderr[-500:])

@@ -6,6 +6,7 @@ TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
+ROOT=$PWD
 export TMPDIR=/tmp
 for step in "$@"; do
   echo "=== $step" | tee -a $OUT/steps.txt
@@ -15,13 +16,13 @@ for step in "$@"; do
     all_tests) timeout 3400 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $OUT/all_tests.txt ;;
     sweep) timeout 1500 python tools/ldpc_size_sweep.py --out $OUT/ldpc_size_sweep.json 2>&1 | tee $OUT/ldpc_size_sweep.txt ;;
     sweep_quick) timeout 900 python tools/ldpc_size_sweep.py --quick --out $OUT/ldpc_size_sweep_quick.json 2>&1 | tee $OUT/ldpc_size_sweep_quick.txt ;;
-    bench) timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 6000 $OUT/bench.json ;;
-    bench_prof) (cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 > $OUT/bench_prof.json 2> $OUT/bench_prof.err); python tools/prof_summary.py $OUT/prof/bench_results.db > $OUT/kernel_stats.txt 2>&1; head -40 $OUT/kernel_stats.txt ;;
-    pmc)  # PMC passes for the kernels of the default bench command (separate runs, --pmc with --kernel-trace only), then the
+    bench) timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 6000 $OUT/bench.json ;;
+    bench_prof) (cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python $ROOT/bench.py --full --steps 5 --warmup 2 > $OUT/bench_prof.json 2> $OUT/bench_prof.err); python tools/prof_summary.py $OUT/prof/bench_results.db > $OUT/kernel_stats.txt 2>&1; head -40 $OUT/kernel_stats.txt ;;
+    pmc)  # PMC passes for the kernels of `bench.py --full` (separate runs, --pmc with --kernel-trace only), then the
           # per-unit counters file bench.py reads (copy $OUT/pmc/counters.json to profiles/counters.json, summary to profiles/)
       mkdir -p $OUT/pmc
       runpmc() { local name=$1; shift; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc/$name -o p -- \
-                 python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc/$name.log 2>&1); }
+                 python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc/$name.log 2>&1); }
       runpmc sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
       runpmc sq2 SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_SCA
       runpmc sq3 SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE
