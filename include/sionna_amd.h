@@ -839,6 +839,38 @@ int samd_lmmse_matrix_c64(const float* h, const float* s, int64_t n, int m, int 
 int samd_lmmse_matrix_c128(const double* h, const double* s, int64_t n, int m, int k, double* g, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Linear precoding at the transmitter (csrc/precoding.hip), complex64 (_c64) and complex128 (_c128, precision = "double").
+ * Interleaved complex, row-major, naturally aligned.  G = V D with unit-norm columns (D = diag(1 / ||v_k||), a zero column
+ * stays zero), V = H^H (H H^H + alpha I)^-1 (RZF, mimo/precoding.py:12-88) or V = H^H (CBF, mimo/precoding.py:91-155).
+ * 1 <= K <= M, K <= 16, M <= 32; anything else returns SAMD_ERR_INVALID.  alpha: DEVICE array of the real type, one
+ * value per item, or NULL and the scalar alpha0 for every item.
+ *   samd_precoding_matrix   rzf_precoding_matrix / cbf_precoding_matrix / rzf_precoder (mimo/precoding.py:157-244):
+ *                           h [n,K,M], x [n,K] -> g [n,M,K] and / or x_precoded [n,M] = G x (either output may be
+ *                           NULL, not both; x only read when x_precoded != NULL); mode SAMD_PRECODE_RZF / _CBF
+ *   samd_rzf_precode_ofdm   RZFPrecoder.call (ofdm/precoding.py:118-177): x [B,TX,K,T,F], h [B,RX,RXA,TX,M,T,F],
+ *                           alpha [B,TX,T,F] or NULL; precoding_ind DEVICE int32 [TX, num_rx_per_tx] receiver indices
+ *                           (StreamManagement.precoding_ind, each in [0, RX)), K = num_rx_per_tx * RXA; eff_pos DEVICE
+ *                           int32 [F]: position of subcarrier f among the num_eff_sc effective subcarriers
+ *                           (ResourceGrid.effective_subcarrier_ind), -1 for a nulled one.  Writes x_precoded
+ *                           [B,TX,M,T,F] and, when h_eff != NULL, the effective channel h_eff [B,RX,RXA,TX,K,T,num_eff_sc]
+ *                           = H_r G for EVERY receiver r (ofdm/precoding.py:81-116 followed by RemoveNulledSubcarriers).
+ * ---------------------------------------------------------------------------------- */
+#define SAMD_PRECODE_RZF 0
+#define SAMD_PRECODE_CBF 1
+int samd_precoding_matrix_c64(const float* h, const float* x, const float* alpha, float alpha0, int64_t n, int k, int m,
+                              int mode, float* g, float* x_precoded, void* stream);
+int samd_precoding_matrix_c128(const double* h, const double* x, const double* alpha, double alpha0, int64_t n, int k, int m,
+                               int mode, double* g, double* x_precoded, void* stream);
+int samd_rzf_precode_ofdm_c64(const float* x, const float* h, const float* alpha, float alpha0, const int32_t* precoding_ind,
+                              const int32_t* eff_pos, int batch, int num_tx, int num_streams, int num_rx, int num_rx_ant,
+                              int num_tx_ant, int num_rx_per_tx, int num_ofdm_symbols, int fft_size, int num_eff_sc,
+                              float* x_precoded, float* h_eff, void* stream);
+int samd_rzf_precode_ofdm_c128(const double* x, const double* h, const double* alpha, double alpha0,
+                               const int32_t* precoding_ind, const int32_t* eff_pos, int batch, int num_tx, int num_streams,
+                               int num_rx, int num_rx_ant, int num_tx_ant, int num_rx_per_tx, int num_ofdm_symbols,
+                               int fft_size, int num_eff_sc, double* x_precoded, double* h_eff, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

@@ -61,6 +61,10 @@ _SIGNATURES = {
     "samd_whiten_channel_c128": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "samd_lmmse_matrix_c64": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "samd_lmmse_matrix_c128": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "samd_precoding_matrix_c64": (_i32, [_vp, _vp, _vp, _f32, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "samd_precoding_matrix_c128": (_i32, [_vp, _vp, _vp, _f64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "samd_rzf_precode_ofdm_c64": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp] + [_i32] * 10 + [_vp, _vp, _vp]),
+    "samd_rzf_precode_ofdm_c128": (_i32, [_vp, _vp, _vp, _f64, _vp, _vp] + [_i32] * 10 + [_vp, _vp, _vp]),
     "samd_cir_to_time_c128": (_i32, [_f64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_apply_time_channel_c128": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_scramble_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),

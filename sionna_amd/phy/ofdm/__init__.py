@@ -8,3 +8,4 @@ from .equalization import OFDMEqualizer, LMMSEEqualizer, ZFEqualizer, MFEqualize
 from .detection import LinearDetector, MMSEPICDetector, EPDetector, KBestDetector, MaximumLikelihoodDetector, \
     MaximumLikelihoodDetectorWithPrior
 from .modulator import OFDMModulator, OFDMDemodulator
+from .precoding import RZFPrecoder
