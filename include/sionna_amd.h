@@ -871,6 +871,43 @@ int samd_rzf_precode_ofdm_c128(const double* x, const double* h, const double* a
                                int fft_size, int num_eff_sc, double* x_precoded, double* h_eff, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Convolutional codes (csrc/conv.hip), float32 (_f32) and float64 (_f64, precision = "double").
+ * The code: polys HOST array of conv_n generator polynomials (bit constraint_length-1-i of polys[p] = character i of
+ * the reference's 0/1 string, e.g. "1101" -> 13), 1 <= conv_n <= 8, constraint_length 3..8, rsc: the first polynomial
+ * is the feedback polynomial (fec/conv/utils.py:81-190, the trellis is built as Trellis._generate_transitions).
+ * T = n / conv_n trellis steps; k = T - (terminate ? constraint_length - 1 : 0) information bits.
+ *   samd_conv_encode        ConvEncoder.call (fec/conv/encoding.py:221-292): u [batch,k] bits -> c [batch,n],
+ *                           n = conv_n (k + (terminate ? constraint_length - 1 : 0))
+ *   samd_conv_viterbi       ViterbiDecoder.call (fec/conv/decoding.py:236-453): y [batch,n] LLRs (method 0, soft_llr) or
+ *                           0/1 values (method 1, hard) -> out [batch,k] information bits (return_info_bits) or
+ *                           [batch,n] codeword bits along the survivor path
+ *   samd_conv_bcjr          BCJRDecoder.call (fec/conv/decoding.py:700-943): llr_ch [batch,n], llr_a [batch,T] or NULL
+ *                           -> out [batch,k] LLRs or hard decisions; algorithm SAMD_CONV_MAP / _LOG / _MAXLOG
+ * Decoders need a device workspace of samd_conv_workspace_bytes(decoder 0 Viterbi / 1 BCJR, constraint_length, T,
+ * batch, dbl) bytes (0: everything in LDS; then workspace may be NULL); SAMD_ERR_WORKSPACE when it is smaller.
+ * ---------------------------------------------------------------------------------- */
+#define SAMD_CONV_MAP 0
+#define SAMD_CONV_LOG 1
+#define SAMD_CONV_MAXLOG 2
+int samd_conv_encode_f32(const float* u, int64_t batch, int k, const uint32_t* polys, int conv_n, int constraint_length,
+                         int rsc, int terminate, float* c, void* stream);
+int samd_conv_encode_f64(const double* u, int64_t batch, int k, const uint32_t* polys, int conv_n, int constraint_length,
+                         int rsc, int terminate, double* c, void* stream);
+size_t samd_conv_workspace_bytes(int decoder, int constraint_length, int num_syms, int64_t batch, int dbl);
+int samd_conv_viterbi_f32(const float* y, int64_t batch, int n, const uint32_t* polys, int conv_n, int constraint_length,
+                          int rsc, int terminate, int method, int return_info_bits, float* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int samd_conv_viterbi_f64(const double* y, int64_t batch, int n, const uint32_t* polys, int conv_n, int constraint_length,
+                          int rsc, int terminate, int method, int return_info_bits, double* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int samd_conv_bcjr_f32(const float* llr_ch, const float* llr_a, int64_t batch, int n, const uint32_t* polys, int conv_n,
+                       int constraint_length, int rsc, int terminate, int algorithm, int hard_out, float* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int samd_conv_bcjr_f64(const double* llr_ch, const double* llr_a, int64_t batch, int n, const uint32_t* polys, int conv_n,
+                       int constraint_length, int rsc, int terminate, int algorithm, int hard_out, double* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

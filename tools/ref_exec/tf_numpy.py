@@ -590,6 +590,21 @@ def make_tf():
     for _n in ("reduce_sum", "reduce_prod", "reduce_min", "reduce_max", "reduce_mean", "reduce_any", "reduce_all", "argmax", "argmin"):
         if hasattr(tf, _n):
             setattr(tf.math, _n, getattr(tf, _n))
+    # ---- ops of the convolutional-code blocks (fec/conv/*.py)
+    TensorArray.stack = lambda self: _t(np.stack([np.asarray(self._items[i]) for i in sorted(self._items)]))
+    tf.unstack = lambda x, num=None, axis=0, **k: [_t(a) for a in np.moveaxis(np.asarray(x), axis, 0)]
+    _gather_nd_plain = tf.gather_nd                            # batch_dims=0 semantics, unchanged
+
+    def _gather_nd(params, indices, batch_dims=0, **k):
+        # only fec/conv/decoding.py:254 passes batch_dims (= 1): indices index each batch item's own params
+        if not batch_dims:
+            return _gather_nd_plain(params, indices, **k)
+        p, idx = np.asarray(params), np.asarray(indices).astype(np.int64)
+        bd = int(batch_dims)
+        assert p.shape[:bd] == idx.shape[:bd]
+        b = np.indices(idx.shape[:-1])[:bd]
+        return _t(p[tuple(b) + tuple(np.moveaxis(idx, -1, 0))])
+    tf.gather_nd = _gather_nd
     return tf
 
 
