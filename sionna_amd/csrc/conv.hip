@@ -475,9 +475,9 @@ int encode(const R* u, int64_t batch, int k, const uint32_t* polys, int conv_n, 
   int rc = build_trellis(polys, conv_n, constraint_length, rsc, &tr);
   if (rc != SAMD_OK) return rc;
   SAMD_REQUIRE(batch >= 0 && k >= 0, "ConvEncoder: invalid dimensions");
-  if (batch == 0 || k == 0) return SAMD_OK;
+  const int T = k + (terminate ? tr.mu : 0);               // k = 0 terminated: the mu tail symbols are still written
+  if (batch == 0 || T == 0) return SAMD_OK;
   SAMD_REQUIRE(u && c, "null argument");
-  const int T = k + (terminate ? tr.mu : 0);
   hipStream_t s = (hipStream_t)stream;
   if (!rsc) {
     const int64_t total = batch * (int64_t)T;

@@ -1,6 +1,8 @@
 """Convolutional encoding - mirror of reference src/sionna/phy/fec/conv/encoding.py: ``ConvEncoder`` (:10-292) on the HIP
 kernels ``samd_conv_encode_f32`` / ``_f64`` (csrc/conv.hip: feed-forward codes one lane per output symbol, recursive
 systematic codes one lane per codeword)."""
+import math
+
 import torch
 
 from .... import _ffi
@@ -95,7 +97,7 @@ class ConvEncoder(Block):
         dbl = self.precision == "double"
         u = _ffi.to_device(bits, torch.float64 if dbl else torch.float32)
         lead = tuple(u.shape[:-1])
-        u2 = u.reshape(-1, self._k).contiguous()
+        u2 = u.reshape(math.prod(lead), self._k).contiguous()       # not -1: k = 0 (terminated, the tail alone) is allowed
         out = torch.empty((u2.shape[0], self._n), dtype=u.dtype, device=u.device)
         fn = _ffi.lib().samd_conv_encode_f64 if dbl else _ffi.lib().samd_conv_encode_f32
         _ffi.check(fn(_ffi.ptr(u2), u2.shape[0], self._k, self._polys.ctypes.data, self._conv_n, self._cl, int(self._rsc),

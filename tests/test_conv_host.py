@@ -1,12 +1,14 @@
 """Convolutional codes on the CPU: the specification tests/conv_f32.py against the reference-executed fixture
 (tests/golden/conv_ref_golden.npz, tools/gen_conv_ref_golden.py) and the reference's own test vectors
-(conv_ref_vectors.npz), the host trellis, the signatures, the argument checks and the import path."""
+(conv_ref_vectors.npz), the host trellis, the signatures, the argument checks and the import path; and the preconditions of
+the anchored bar of tests/test_gpu_conv_edges.py (tests/conv_cases.py) on the inputs that module draws."""
 import json
 import os
 
 import numpy as np
 import pytest
 
+import conv_cases as cc
 import conv_f32 as spec
 from sionna_amd.phy.fec.conv import BCJRDecoder, ConvEncoder, Trellis, ViterbiDecoder, polynomial_selector
 
@@ -98,6 +100,48 @@ def test_spec_double_precision_agrees_with_single():
     assert np.array_equal(spec.viterbi(llr, gp, rsc, term, dtype=np.float64), G[p + "vit_soft_llr"])
     d = spec.bcjr(llr, gp, rsc, term, "map", hard_out=False, dtype=np.float64)
     assert np.all(np.abs(d - G[p + "bcjr_map"]) <= spec.llr_bar(llr)[:, None])
+
+
+@pytest.mark.parametrize("alg,factor", [("map", 100.), ("log", 10.)])
+@pytest.mark.parametrize("case", cc.SOFT_CASES, ids=cc.case_id)
+def test_anchor_of_the_soft_bar_is_far_below_llr_bar(case, alg, factor):
+    """the float32 specification lies within llr_bar / 100 (map) and llr_bar / 10 (log) of its float64 instantiation on
+    every input of test_gpu_conv_edges.py, so the anchored bar 2 max |ref32 - ref64| + ulp stays below llr_bar"""
+    _, _, _, llr, la = cc.inputs(case)
+    for with_a, (r32, r64) in cc.refs(case, alg).items():
+        assert r32.dtype == np.float32 and r64.dtype == np.float64
+        assert np.all(np.isfinite(r32)) and np.all(np.isfinite(r64))
+        bar = spec.llr_bar(llr, la if with_a else None)
+        err = np.max(np.abs(r32.astype(np.float64) - r64), axis=-1)
+        assert np.all(factor * err < bar), (with_a, float(np.max(err / bar)))
+        assert np.all(cc.anchored_bar(r32, r64) < bar)
+
+
+def test_map_strong_amp_is_the_largest_finite_one():
+    """float32 map under strong LLRs: exp(bm) leaves the float32 range; MAP_STRONG_AMP is the largest amplitude of
+    MAP_AMPS at which the specification is finite on every STRONG case, with and without llr_a"""
+    finite = {amp: all(np.all(np.isfinite(r32)) for case in cc.STRONG for r32, _ in cc.refs(case, "map", amp).values())
+              for amp in cc.MAP_AMPS + cc.STRONG_AMPS}
+    assert max(a for a in cc.MAP_AMPS if finite[a]) == cc.MAP_STRONG_AMP
+    assert not any(finite[a] for a in cc.STRONG_AMPS)
+
+
+@pytest.mark.parametrize("amp", cc.STRONG_AMPS)
+def test_log_spec_is_finite_under_strong_llrs(amp):
+    for case in cc.STRONG:
+        _, _, _, llr, la = cc.inputs(case, amp)
+        for with_a, (r32, r64) in cc.refs(case, "log", amp).items():
+            assert np.all(np.isfinite(r32)) and np.all(np.isfinite(r64))
+            assert np.all(cc.anchored_bar(r32, r64) < spec.llr_bar(llr, la if with_a else None))
+
+
+def test_spec_of_the_tail_alone():
+    """k = 0 with termination: mu zero symbols, decoded to nothing"""
+    for rsc in (False, True):
+        c = spec.encode(np.zeros((3, 0)), ("1101", "1011"), rsc, True)
+        assert c.shape == (3, 6) and not c.any()
+        assert spec.viterbi(c.astype(np.float32), ("1101", "1011"), rsc, True).shape == (3, 0)
+        assert spec.bcjr(c.astype(np.float32), ("1101", "1011"), rsc, True).shape == (3, 0)
 
 
 def test_signatures_match_the_reference():
