@@ -908,6 +908,23 @@ int samd_conv_bcjr_f64(const double* llr_ch, const double* llr_a, int64_t batch,
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Ordered-statistics decoding (csrc/osd.hip), float32 (_f32) and float64 (_f64, precision = "double").
+ *   samd_osd_decode         OSDecoder.call (fec/linear/decoding.py:415-478) with _find_mrb (:318-402), _find_min_dist
+ *                           (:272-316) and _get_dist (:237-270): llr [batch,n] -> out [batch,n] hard decisions of the
+ *                           codeword bits.  gm_rows: DEVICE generator matrix [k][(n + 63) / 64] packed by rows, bit j & 63
+ *                           of word j >> 6 = G[r][j]; it must have rank k.  t: the order (orders above k add nothing).
+ * Refused with SAMD_ERR_INVALID: n - k > 512, a packed matrix beyond the 64 KB LDS budget (every code with n <= 512
+ * fits), and a t whose number of candidates sum_i C(k,i) does not fit 62 bits.  The device workspace holds
+ * samd_osd_workspace_bytes(k, n, t, batch) bytes (0 for a refused code), 8-byte aligned; batches beyond 4096
+ * codewords reuse it trip by trip.  tests/osd_f32.py is the specification (decisions identical to it).
+ * ---------------------------------------------------------------------------------- */
+size_t samd_osd_workspace_bytes(int k, int n, int t, int64_t batch);
+int samd_osd_decode_f32(const float* llr, const uint64_t* gm_rows, int64_t batch, int k, int n, int t, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int samd_osd_decode_f64(const double* llr, const uint64_t* gm_rows, int64_t batch, int k, int n, int t, double* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

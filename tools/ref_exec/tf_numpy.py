@@ -228,7 +228,7 @@ def make_tf():
         return _t(np.arange(*[np.asarray(v).item() for v in a]).astype(dtype))
     tf.range = _range
     tf.is_tensor = lambda x: isinstance(x, (Tensor, RaggedTensor))
-    tf.shape = lambda x, **k: _t(np.array(np.asarray(x).shape, dtype=np.int32))
+    tf.shape = lambda x, out_type=np.int32, **k: _t(np.array(np.asarray(x).shape, dtype=out_type))
     tf.rank = lambda x, **k: np.asarray(x).ndim
     tf.executing_eagerly = lambda: True
     tf.size = lambda x: np.asarray(x).size
