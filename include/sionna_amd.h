@@ -925,6 +925,34 @@ int samd_osd_decode_f64(const double* llr, const uint64_t* gm_rows, int64_t batc
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Batched FIR filtering with zero insertion and decimation folded into the indexing (csrc/signal.hip):
+ *   samd_upfirdn            convolve (signal/utils.py:13-159; the four real sums of :122-151), Filter.call
+ *                           (signal/filter.py:268-285), and around it Upsampling.call (signal/upsampling.py:57-65) and
+ *                           Downsampling.call (signal/downsampling.py:59-72) in ONE launch:
+ *                             y[b, m] = sum_{k = 0..K-1} h[k] * xu[b, start + m * down - k],
+ *                             xu[b, j] = x[b, j / up] if j % up == 0 and 0 <= j / up < N, else 0.
+ *                           x [B, N], out [B, M], taps h_re [K] and h_im [K] (h_im NULL: real taps); conjugate != 0 negates
+ *                           the taps' imaginary part.  With L = N * up, padding "full" is start = 0, M = L + K - 1; "same"
+ *                           start = (K - 1) / 2 (integer division), M = L; "valid" start = K - 1, M = L - K + 1.
+ * _f32 / _f64 take real x (out is real for real taps, interleaved complex for complex taps); _c64 / _c128 take
+ * interleaved complex x and write interleaved complex out.  Arithmetic (tests/signal_f32.py is the specification, results
+ * are bit-identical to it): every real sum starts at +0 and adds h[k] * x[.] in ascending k, one multiplication and one
+ * addition, over the k whose sample exists; a complex output is (rr - ii) + j (ri + ir) of the sums real x real,
+ * imag x imag, x real x tap imag, x imag x tap real; real taps use rr and ir only, real x uses rr and ri only.
+ * Refused with SAMD_ERR_INVALID: K > SAMD_UPFIRDN_MAX_TAPS, N * up + K >= 2^31, and a ratio down / up whose input tile
+ * of 256 outputs (255 * down / up + (K - 1) / up + 3 samples, with the taps) exceeds 64 KB of LDS.
+ * ---------------------------------------------------------------------------------- */
+#define SAMD_UPFIRDN_MAX_TAPS 1025
+int samd_upfirdn_f32(const float* x, const float* h_re, const float* h_im, int64_t B, int64_t N, int K, int up,
+                     int64_t start, int down, int64_t M, int conjugate, float* out, void* stream);
+int samd_upfirdn_f64(const double* x, const double* h_re, const double* h_im, int64_t B, int64_t N, int K, int up,
+                     int64_t start, int down, int64_t M, int conjugate, double* out, void* stream);
+int samd_upfirdn_c64(const float* x, const float* h_re, const float* h_im, int64_t B, int64_t N, int K, int up,
+                     int64_t start, int down, int64_t M, int conjugate, float* out, void* stream);
+int samd_upfirdn_c128(const double* x, const double* h_re, const double* h_im, int64_t B, int64_t N, int K, int up,
+                      int64_t start, int down, int64_t M, int conjugate, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

@@ -75,6 +75,10 @@ _SIGNATURES = {
     "samd_osd_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64]),
     "samd_osd_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "samd_osd_decode_f64": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "samd_upfirdn_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "samd_upfirdn_f64": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "samd_upfirdn_c64": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "samd_upfirdn_c128": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp, _vp]),
     "samd_cir_to_time_c128": (_i32, [_f64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_apply_time_channel_c128": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_scramble_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),

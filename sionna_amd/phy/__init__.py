@@ -2,6 +2,7 @@
 from .config import config, dtypes
 from .block import Block, Object, Tensor
 from . import mapping, utils, channel, mimo, ofdm
+from . import signal
 from . import fec
 from . import nr
 from .fec import ldpc

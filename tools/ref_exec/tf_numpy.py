@@ -537,6 +537,23 @@ def make_tf():
     def pad(tensor, paddings, mode="CONSTANT", constant_values=0, name=None):
         return _t(np.pad(np.asarray(tensor), [(int(a), int(b)) for a, b in np.asarray(paddings)], constant_values=constant_values))
     tf.pad = pad
+    def _convolution(input, filters, strides=None, padding="VALID", **k):
+        """tf.nn.convolution of [batch, width, 1] with [taps, 1, 1], stride 1 (signal/utils.py:132-146): a correlation;
+        "SAME" pads taps - 1 zeros in all, the smaller half to the left.  Accumulated in float64, returned in the input's dtype."""
+        x, f = np.asarray(input), np.asarray(filters)
+        assert x.ndim == 3 and x.shape[-1] == 1 and f.ndim == 3 and f.shape[1:] == (1, 1) and strides in (None, 1)
+        x2, taps = x[..., 0].astype(np.float64), f[:, 0, 0].astype(np.float64)
+        if padding.upper() == "SAME":
+            total = len(taps) - 1
+            x2 = np.pad(x2, [(0, 0), (total // 2, total - total // 2)])
+        else:
+            assert padding.upper() == "VALID"
+        win = np.lib.stride_tricks.sliding_window_view(x2, len(taps), axis=-1)
+        return _t((win @ taps).astype(x.dtype)[..., None])
+    tf.nn.convolution = _convolution
+    _mean_scalar_axis = tf.reduce_mean                              # the axes may arrive as a tensor (signal/utils.py:299)
+    tf.reduce_mean = lambda x, axis=None, keepdims=False, name=None: _mean_scalar_axis(
+        x, axis if axis is None or np.isscalar(axis) else tuple(int(a) for a in np.asarray(axis).ravel()), keepdims)
     tf.repeat = lambda x, repeats, axis=None, **k: _t(np.repeat(np.asarray(x), repeats, axis=axis))
     tf.reverse = lambda x, axis, **k: _t(np.flip(np.asarray(x), axis=tuple(int(a) for a in np.atleast_1d(axis))))
     tf.linspace = lambda start, stop, num, **k: _t(np.linspace(start, stop, int(num)).astype(
