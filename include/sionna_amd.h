@@ -953,6 +953,30 @@ int samd_upfirdn_c128(const double* x, const double* h_re, const double* h_im, i
                       int64_t start, int down, int64_t M, int conjugate, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * PUSCH slot grids from the scrambled coded bits in ONE launch (csrc/pusch.hip): the four passes of PUSCHTransmitter.call
+ * (nr/pusch_transmitter.py:217-230) after the transport-block encoder -
+ *   Mapper.call               mapping.py:497-519              m bits -> label (MSB first) -> constellation point
+ *   LayerMapper.call          nr/layer_mapping.py:165-189     symbol i of the codeword -> layer i mod num_layers
+ *   ResourceGridMapper.call   ofdm/resource_grid.py:394-412   data symbols and pilots onto the grid, zeros elsewhere
+ *   PUSCHPrecoder.call        nr/pusch_precoder.py:71-95      x[port] = sum_layer W[port, layer] * grid[layer]
+ * bits float32 0/1 [batch, num_tx, num_data * num_layers * m] with m = num_bits_per_symbol (even, 2..10): data symbol s of
+ * layer l reads bits (s * num_layers + l) * m ... + m - 1.  points DEVICE [2^m]; pilots DEVICE [S, num_pilots] with
+ * S = num_tx * num_layers (NULL if num_pilots = 0); data_pos / pilot_pos DEVICE int32 [S, num_re] as in samd_rg_map_c64 (-1:
+ * absent; where both are absent the layer carries zero).  w DEVICE [num_tx, num_ports, num_layers], or NULL: then
+ * num_ports must equal num_layers and the layer grids are written through.  out [batch, num_tx, num_ports, num_re].
+ * 1 <= num_layers, num_ports <= 4.  _c64: points, pilots, w, out interleaved complex64; _c128: complex128 (bits float32).
+ * Arithmetic (tests/pusch_f32.py is the specification, results are bit-identical to it): per port, re and im start at +0
+ * and add, in ascending layer order, (wr * xr - wi * xi) and (wr * xi + wi * xr): four products, a difference, a sum and
+ * the two accumulations, each rounded once, no fused multiply-add.
+ * ---------------------------------------------------------------------------------- */
+int samd_pusch_grid_c64(const float* bits, const float* points, const float* pilots, const int32_t* data_pos,
+                        const int32_t* pilot_pos, const float* w, int64_t batch, int num_tx, int num_layers, int num_ports,
+                        int num_re, int num_data, int num_pilots, int num_bits_per_symbol, float* out, void* stream);
+int samd_pusch_grid_c128(const float* bits, const double* points, const double* pilots, const int32_t* data_pos,
+                         const int32_t* pilot_pos, const double* w, int64_t batch, int num_tx, int num_layers, int num_ports,
+                         int num_re, int num_data, int num_pilots, int num_bits_per_symbol, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

@@ -1,4 +1,14 @@
-"""5G NR transport-block chain (mirror of the ``TBEncoder`` / ``TBDecoder`` part of ``sionna.phy.nr``)."""
-from .utils import generate_prng_seq, calculate_num_coded_bits, calculate_tb_size
+"""5G NR: the transport-block chain and the PUSCH transmitter with its configuration objects (mirror of ``sionna.phy.nr``
+without the receiver: ``PUSCHReceiver`` and ``PUSCHLSChannelEstimator`` are not built)."""
+from .utils import generate_prng_seq, decode_mcs_index, calculate_num_coded_bits, calculate_tb_size
+from .config import Config
+from .carrier_config import CarrierConfig
+from .pusch_dmrs_config import PUSCHDMRSConfig
+from .tb_config import TBConfig
+from .pusch_config import PUSCHConfig, check_pusch_configs
+from .pusch_pilot_pattern import PUSCHPilotPattern
+from .layer_mapping import LayerMapper, LayerDemapper
+from .pusch_precoder import PUSCHPrecoder
 from .tb_encoder import TBEncoder
 from .tb_decoder import TBDecoder
+from .pusch_transmitter import PUSCHTransmitter

@@ -1,7 +1,9 @@
 """5G NR helpers of the transport-block chain - mirror of reference src/sionna/phy/nr/utils.py
-(``generate_prng_seq`` :14-78, ``calculate_num_coded_bits`` :374-471, ``calculate_tb_size``
-:473-805).  Scalar arguments (the TB blocks only need scalars); init-time host arithmetic in the
+(``generate_prng_seq`` :14-78, ``decode_mcs_index`` :80-304, ``calculate_num_coded_bits`` :374-471,
+``calculate_tb_size`` :473-805).  Scalar arguments (the TB blocks only need scalars); init-time host arithmetic in the
 reference's float32."""
+import functools
+
 import numpy as np
 import torch
 
@@ -26,6 +28,88 @@ def generate_prng_seq(length, c_init):
     _ffi.check(_ffi.lib().samd_nr_prng_seq_f32(int(c_init), int(length), _ffi.ptr(out), _ffi.stream()),
                "generate_prng_seq")
     return out.cpu().numpy()
+
+
+@functools.lru_cache(maxsize=256)
+def _prng_seq_host(length, c_init):
+    """the same sequence on the host, int8 and read-only: c(n) = x1(n + 1600) + x2(n + 1600) mod 2 with
+    x1(n + 31) = x1(n + 3) + x1(n), x2(n + 31) = x2(n + 3) + x2(n + 2) + x2(n + 1) + x2(n), x1 = 1, x2 = c_init at the start
+    (38.211 Sec. 5.2.1).  The configuration objects build the DMRS from it without a device."""
+    assert 0 <= int(c_init) < 2 ** 32 and int(length) > 0
+    total = int(length) + 1600
+    x1, x2 = np.zeros(total + 31, np.int8), np.zeros(total + 31, np.int8)
+    x1[0] = 1
+    x2[:31] = (int(c_init) >> np.arange(31)) & 1
+    for i in range(total):
+        x1[i + 31] = x1[i + 3] ^ x1[i]
+        x2[i + 31] = x2[i + 3] ^ x2[i + 2] ^ x2[i + 1] ^ x2[i]
+    c = x1[1600:total] ^ x2[1600:total]
+    c.setflags(write=False)
+    return c
+
+
+# 38.214 Tables 6.1.4.1-1 / -2 (PUSCH with transform precoding; the entries that depend on q are written for q = 1) and
+# 5.1.3.1-1 .. -4: modulation order and target code rate x 1024 per MCS index, -1 where the index is reserved
+_MCS_ORDER = np.array([
+    [[1] * 2 + [2] * 8 + [4] * 7 + [6] * 11 + [-1],
+     [1] * 6 + [2] * 10 + [4] * 8 + [6] * 4 + [-1],
+     [-1] * 29,
+     [-1] * 29],
+    [[2] * 10 + [4] * 7 + [6] * 12,
+     [2] * 5 + [4] * 6 + [6] * 9 + [8] * 8 + [-1],
+     [2] * 15 + [4] * 6 + [6] * 8,
+     [2] * 3 + [4] * 3 + [6] * 9 + [8] * 8 + [10] * 4 + [-1] * 2]], np.int32)
+_MCS_RATE = np.array([
+    [[240, 314, 193, 251, 308, 379, 449, 526, 602, 679, 340, 378, 434, 490, 553, 616, 658, 466, 517, 567, 616, 666, 719, 772,
+      822, 873, 910, 948, -1],
+     [60, 80, 100, 128, 156, 198, 120, 157, 193, 251, 308, 379, 449, 526, 602, 679, 378, 434, 490, 553, 616, 658, 699, 772,
+      567, 616, 666, 772, -1],
+     [-1] * 29,
+     [-1] * 29],
+    [[120, 157, 193, 251, 308, 379, 449, 526, 602, 679, 340, 378, 434, 490, 553, 616, 658, 438, 466, 517, 567, 616, 666, 719,
+      772, 822, 873, 910, 948],
+     [120, 193, 308, 449, 602, 378, 434, 490, 553, 616, 658, 466, 517, 567, 616, 666, 719, 772, 822, 873, 682.5, 711, 754,
+      797, 841, 885, 916.5, 948, -1],
+     [30, 40, 50, 64, 78, 99, 120, 157, 193, 251, 308, 379, 449, 526, 602, 340, 378, 434, 490, 553, 616, 438, 466, 517, 567,
+      616, 666, 719, 772],
+     [120, 193, 449, 378, 490, 616, 466, 517, 567, 616, 666, 719, 772, 822, 873, 682.5, 711, 754, 797, 841, 885, 916.5, 948,
+      805.5, 853, 900.5, 948, -1, -1]]], np.float32)
+
+
+def decode_mcs_index(mcs_index, table_index=1, is_pusch=True, transform_precoding=False, pi2bpsk=False,
+                     check_index_validity=True, verbose=False):
+    """Modulation order (int32) and target code rate (float32) of an MCS index, 38.214 Sec. 5.1.3.1 / 6.1.4.1
+    (utils.py:80-304).  Scalars or arrays of one shape; NumPy values, since the configuration objects live on the host."""
+    mcs_index = np.asarray(mcs_index).astype(np.int32)
+    shape = mcs_index.shape
+
+    def shaped(v, dtype):
+        v = np.asarray(v)
+        assert v.shape in ((), shape), "inconsistent input shapes"
+        return np.broadcast_to(v.astype(dtype), shape)
+
+    table_index = shaped(table_index, np.int32)
+    is_pusch, transform_precoding, pi2bpsk = shaped(is_pusch, bool), shaped(transform_precoding, bool), shaped(pi2bpsk, bool)
+    assert np.all(mcs_index >= 0), "MCS index cannot be negative"
+    assert np.all(mcs_index <= 28), "MCS index cannot be higher than 28"
+    assert np.all(np.isin(table_index, [1, 2, 3, 4])), "table_index must contain values in [1,2,3,4]"
+    if verbose:
+        print(f"Selected MCS index {mcs_index} for {np.where(is_pusch, 'PUSCH', 'PDSCH')} channel and Table index {table_index}.")
+    # row 0: PUSCH with transform precoding; row 1: PDSCH, and PUSCH without it
+    row = (~is_pusch | ~transform_precoding).astype(np.int32)
+    order = _MCS_ORDER[row, table_index - 1, mcs_index]
+    rate = _MCS_RATE[row, table_index - 1, mcs_index]
+    if check_index_validity and np.any(order < 0):
+        raise ValueError("Invalid MCS index")
+    # tp-pi2BPSK: q = 1, else q = 2, on the first entries of the two transform-precoding tables
+    on_q = (row == 0) & (((table_index == 1) & (mcs_index < 2)) | ((table_index == 2) & (mcs_index < 6)))
+    q = np.where(pi2bpsk, 1, 2).astype(np.int32)
+    order = np.where(on_q, order * q, order).astype(np.int32)
+    rate = (np.where(on_q, rate / q.astype(np.float32), rate) / np.float32(1024)).astype(np.float32)
+    if verbose:
+        print(f"Modulation order: {order}")
+        print(f"Target code rate: {rate}")
+    return order[()], rate[()]
 
 
 def calculate_num_coded_bits(modulation_order, num_prbs, num_ofdm_symbols, num_dmrs_per_prb, num_layers=1, num_ov=0,

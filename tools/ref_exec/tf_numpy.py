@@ -190,6 +190,7 @@ def make_tf():
     tf = types.ModuleType("tensorflow")
     tf.__doc__ = "NumPy stand-in (tools/ref_exec/tf_numpy.py)"
     tf.Tensor, tf.RaggedTensor = Tensor, RaggedTensor
+    tf.TensorShape = type("TensorShape", (), {})           # shapes are tuples here: nothing is an instance of it
     for name in ("float16", "float32", "float64", "int8", "int16", "int32", "int64", "uint8", "complex64", "complex128", "bool"):
         setattr(tf, name, DType(name))
     tf.bfloat16 = type("BF16", (), {"__eq__": lambda self, o: False, "__hash__": lambda self: 0, "__repr__": lambda self: "tf.bfloat16"})()   # (no NumPy twin; only ever compared)
@@ -560,7 +561,7 @@ def make_tf():
         np.asarray(start).dtype if np.asarray(start).dtype.kind == "f" and not isinstance(start, float) else np.float32))
     tf.math.cumsum = tf.cumsum = lambda x, axis=0, **k: _t(np.cumsum(np.asarray(x), axis=axis))
     tf.experimental = types.SimpleNamespace(numpy=types.SimpleNamespace(
-        swapaxes=lambda x, a, b: _t(np.swapaxes(np.asarray(x), a, b)),
+        swapaxes=lambda x, axis1, axis2: _t(np.swapaxes(np.asarray(x), axis1, axis2)),
         sinc=_elementwise(lambda x: np.sinc(x).astype(x.dtype)),
         log10=_elementwise(np.log10), log2=_elementwise(np.log2)))
     # ---- ops of the 3GPP channel-model code (tr38901/*.py)
