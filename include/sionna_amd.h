@@ -977,6 +977,31 @@ int samd_pusch_grid_c128(const float* bits, const double* points, const double* 
                          int num_re, int num_data, int num_pilots, int num_bits_per_symbol, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * PUSCH DMRS least-squares estimates, de-spread, in ONE launch (csrc/pusch_rx.hip): PUSCHLSChannelEstimator
+ * .estimate_at_pilot_locations (nr/pusch_channel_estimation.py:103-169) behind the pilot gather of BaseChannelEstimator.call
+ * (ofdm/channel_estimation.py:138-173) and, with ``gather``, the spreading of NearestNeighborInterpolator
+ * (ofdm/channel_estimation.py:364-435) -
+ *   ls(p) = y[r, src[s, p]] * coef[s, p]                  coef = 1 / pilot, 0 for a zero pilot (divide_no_nan): ls = +0
+ *   t(p)  = (ls(p) + ls(p')) / 2 with dmrs_length 2       p' the same position of the adjacent DMRS symbol; else t = ls
+ *   h(p)  = (t(g) + ... + t(g + run - 1)) / 2             g the first pilot of p's run, run = 2 * num_cdm_groups_without_data
+ *         = 0 where t(p) = 0                              the reference's cond = |h_hat| > 0: it depends on the data
+ *   out[r, s, j] = h(j) (gather NULL, n_out = num_pilots) or h(gather[s, j]) (gather DEVICE int32 [S, n_out])
+ * y [rows, n_in] with rows = batch * num_rx * num_rx_ant (the full grid, n_in = num_ofdm_symbols * fft_size, or the gathered
+ * pilots, n_in = S * num_pilots); src DEVICE int32 [S, num_pilots]; coef DEVICE [S, num_pilots]; out [rows, S, n_out].
+ * Pilots of a stream are numbered row-major, pilots_per_symbol per DMRS symbol; num_pilots is a multiple of
+ * pilots_per_symbol, that a multiple of run; run is 2, 4 or 6.  A src, gather or coef entry that names nothing gives +0.
+ * _c64: y, coef, out interleaved complex64; _c128: complex128.  Arithmetic (tests/pusch_rx_f32.py is the specification,
+ * results are bit-identical to it): ls re = yr cr - yi ci, im = yr ci + yi cr; the run's sum starts at +0 and adds in
+ * ascending p; every product, sum and halving rounded once, no fused multiply-add.
+ * ---------------------------------------------------------------------------------- */
+int samd_pusch_ls_c64(const float* y, const int32_t* src, const float* coef, const int32_t* gather, int64_t rows,
+                      int num_streams, int num_pilots, int pilots_per_symbol, int run, int dmrs_length, int n_out,
+                      int64_t n_in, float* out, void* stream);
+int samd_pusch_ls_c128(const double* y, const int32_t* src, const double* coef, const int32_t* gather, int64_t rows,
+                       int num_streams, int num_pilots, int pilots_per_symbol, int run, int dmrs_length, int n_out,
+                       int64_t n_in, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

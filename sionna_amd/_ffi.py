@@ -81,6 +81,8 @@ _SIGNATURES = {
     "samd_upfirdn_c128": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp, _vp]),
     "samd_pusch_grid_c64": (_i32, [_vp] * 6 + [_i64] + [_i32] * 7 + [_vp, _vp]),
     "samd_pusch_grid_c128": (_i32, [_vp] * 6 + [_i64] + [_i32] * 7 + [_vp, _vp]),
+    "samd_pusch_ls_c64": (_i32, [_vp] * 4 + [_i64] + [_i32] * 6 + [_i64, _vp, _vp]),
+    "samd_pusch_ls_c128": (_i32, [_vp] * 4 + [_i64] + [_i32] * 6 + [_i64, _vp, _vp]),
     "samd_cir_to_time_c128": (_i32, [_f64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_apply_time_channel_c128": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_scramble_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),

@@ -1,5 +1,5 @@
 """Channel utilities of the hot path - mirror of reference src/sionna/phy/channel/utils.py
-(``subcarrier_frequencies`` :15-66, ``cir_to_ofdm_channel`` :180-253)."""
+(``subcarrier_frequencies`` :15-66, ``cir_to_ofdm_channel`` :180-253, ``time_to_ofdm_channel`` :352-457)."""
 import numpy as np
 import torch
 
@@ -37,3 +37,19 @@ def cir_to_ofdm_channel(frequencies, a, tau, normalize=False):
     _ffi.check(fn(_ffi.ptr(a), _ffi.ptr(tau), _ffi.ptr(fr), b, rx, ra, tx, ta, p, t, fr.numel(), int(bool(normalize)),
                   _ffi.ptr(h), _ffi.stream()), "cir_to_ofdm_channel")
     return wrap(h)
+
+
+def time_to_ofdm_channel(h_t, rg, l_min):
+    """Channel frequency response per OFDM symbol from the discrete complex-baseband impulse response
+    (utils.py:352-457): h_t [..., num_time_steps, l_max - l_min + 1] -> [..., num_ofdm_symbols, fft_size].  The taps at the
+    first sample after every cyclic prefix, zero-padded to fft_size, rolled by l_min so that the response starts with lag 0,
+    FFT, zero subcarrier moved to the centre.  Library-shaped work: ``torch.fft`` on the device the tensor lives on (rocFFT
+    for device tensors), in the tensor's own precision."""
+    h = h_t if isinstance(h_t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(h_t)))
+    h = h.as_subclass(torch.Tensor)
+    assert h.is_complex() and h.dim() >= 2, "h_t must be complex with shape [..., num_time_steps, l_max - l_min + 1]"
+    assert h.shape[-1] <= rg.fft_size, "the impulse response is longer than fft_size"
+    h = h[..., rg.cyclic_prefix_length:rg.num_time_samples:rg.fft_size + rg.cyclic_prefix_length, :]
+    h = torch.nn.functional.pad(h, (0, rg.fft_size - h.shape[-1]))
+    h = torch.roll(h, int(l_min), dims=-1)
+    return wrap(torch.fft.fftshift(torch.fft.fft(h, dim=-1), dim=-1).contiguous())

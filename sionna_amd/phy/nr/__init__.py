@@ -1,5 +1,5 @@
-"""5G NR: the transport-block chain and the PUSCH transmitter with its configuration objects (mirror of ``sionna.phy.nr``
-without the receiver: ``PUSCHReceiver`` and ``PUSCHLSChannelEstimator`` are not built)."""
+"""5G NR: the transport-block chain, the PUSCH transmitter with its configuration objects and the PUSCH receiver with its
+DMRS-aware channel estimator (mirror of ``sionna.phy.nr``)."""
 from .utils import generate_prng_seq, decode_mcs_index, calculate_num_coded_bits, calculate_tb_size
 from .config import Config
 from .carrier_config import CarrierConfig
@@ -12,3 +12,5 @@ from .pusch_precoder import PUSCHPrecoder
 from .tb_encoder import TBEncoder
 from .tb_decoder import TBDecoder
 from .pusch_transmitter import PUSCHTransmitter
+from .pusch_channel_estimation import PUSCHLSChannelEstimator
+from .pusch_receiver import PUSCHReceiver

@@ -80,9 +80,23 @@ def params(fn):
     return [p for p in out if p[0] not in ("self", "cls")]
 
 
-def main():
+# the NR PUSCH receiver's public names: a table of their own, tests/golden/pusch_rx_api_signatures.json (--pusch-rx)
+SURFACE_PUSCH_RX = {
+    "nr/pusch_channel_estimation.py": ("nr", ["PUSCHLSChannelEstimator"]),
+    "nr/pusch_receiver.py": ("nr", ["PUSCHReceiver"]),
+    "channel/utils.py": ("channel", ["time_to_ofdm_channel"]),
+}
+OUT_PUSCH_RX = os.path.join(ROOT, "tests", "golden", "pusch_rx_api_signatures.json")
+
+
+def main_pusch_rx():
+    main(SURFACE_PUSCH_RX, OUT_PUSCH_RX)
+
+
+def main(surface=None, out=None):
+    surface, out = surface or SURFACE, out or OUT
     table = {}
-    for rel, (mod, names) in SURFACE.items():
+    for rel, (mod, names) in surface.items():
         path = os.path.join(REF, rel)
         tree = ast.parse(open(path).read())
         found = {}
@@ -104,10 +118,11 @@ def main():
         assert not missing, (rel, missing)
         for n, e in found.items():
             table[f"{mod}.{n}"] = dict(e, file=rel)
-    with open(OUT, "w") as f:
+    with open(out, "w") as f:
         json.dump({"_comment": "reference signatures by ast (tools/gen_api_signatures.py); defaults as source text", "signatures": table}, f, indent=1)
-    print(len(table), "signatures ->", OUT)
+    print(len(table), "signatures ->", out)
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+    main_pusch_rx() if "--pusch-rx" in sys.argv else main()
