@@ -14,6 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import ofdm as o, mapping as omap, utils as outil, mimo_f32 as of32
+import channel_f32 as chf
 
 
 def _same_f32(got, ref):
@@ -109,6 +110,8 @@ def test_cir_to_ofdm_large_links(phy):
             h = _np(phy.channel.cir_to_ofdm_channel(fr, a, tau, normalize=norm))
             ref = o.cir_to_ofdm_channel(fr, a, tau, normalize=norm)
             assert np.allclose(h, ref, rtol=2e-4, atol=5e-5), (ra, ta, p_, t, norm)
+            # and on every output within the bound derived from the kernels' arithmetic (tests/channel_f32.py)
+            assert chf.ratio(h, fr, a, tau, norm) <= 1.0, (ra, ta, p_, t, norm)
     # a link that fits is bit-identical whether its taps come from LDS or from global memory is not observable from
     # here; the small case of test_cir_to_ofdm_and_apply_channel pins the LDS variant against the same oracle
 
