@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <atomic>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/sionna_amd.h"
 
@@ -43,14 +45,28 @@ inline int launch_status() {
 // a machine without a GPU.  Such a handle refuses every launch.
 bool host_only();
 
+// One hipMalloc'd array that its owner's destructor frees (move-only).  assign(): an empty table, or any table of a
+// SAMD_HOST_ONLY handle, stays null with SAMD_OK; a HIP error is reported through set_error as SAMD_ERR_HIP.
 template <typename T>
-inline int upload(T** dst, const T* src, size_t n) {
-  *dst = nullptr;
-  if (n == 0 || host_only()) return SAMD_OK;
-  SAMD_HIP_CHECK(hipMalloc((void**)dst, n * sizeof(T)));
-  SAMD_HIP_CHECK(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return SAMD_OK;
-}
+class DeviceTable {
+ public:
+  DeviceTable() = default;
+  DeviceTable(DeviceTable&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DeviceTable& operator=(DeviceTable&& o) noexcept { std::swap(p_, o.p_); return *this; }
+  ~DeviceTable() { if (p_) (void)hipFree(p_); }
+  int assign(const T* src, size_t n) {
+    *this = DeviceTable();
+    if (n == 0 || host_only()) return SAMD_OK;
+    SAMD_HIP_CHECK(hipMalloc((void**)&p_, n * sizeof(T)));
+    SAMD_HIP_CHECK(hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return SAMD_OK;
+  }
+  int assign(const std::vector<T>& v) { return assign(v.data(), v.size()); }
+  const T* get() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: set it the first time a (kernel,
 // device, size) triple is launched from this process instead of on every launch.  Lock-free: a hash collision or a race

@@ -170,7 +170,7 @@ inline unsigned ygrid(int rows) { return (unsigned)std::max(1, std::min(rows, 40
 
 void launch_cn64(int mode, dim3 grid, hipStream_t st, double* msg, const double* xtot, const samd_ldpc_graph* g,
                  const int32_t* nodes, int n_nodes, int batch, int from_state, double llr_max, double offset) {
-#define SAMD_CN64(M) hipLaunchKernelGGL((cn64_kernel<M>), grid, dim3(64), 0, st, msg, xtot, g->cn_ptr, g->cn_edge, g->cn_vn, nodes, n_nodes, batch, from_state, llr_max, offset)
+#define SAMD_CN64(M) hipLaunchKernelGGL((cn64_kernel<M>), grid, dim3(64), 0, st, msg, xtot, g->cn_ptr.get(), g->cn_edge.get(), g->cn_vn.get(), nodes, n_nodes, batch, from_state, llr_max, offset)
   switch (mode) {
     case SAMD_CN_BOXPLUS: SAMD_CN64(SAMD_CN_BOXPLUS); break;
     case SAMD_CN_BOXPLUS_PHI: SAMD_CN64(SAMD_CN_BOXPLUS_PHI); break;
@@ -676,21 +676,22 @@ extern "C" int samd_ldpc_bp_decode_f64(const samd_ldpc_graph_t* g, const samd_ld
   const int num_sub = sched ? sched->num_sub : 1;
   for (int it = 0; it < num_iter; ++it)
     for (int j = 0; j < num_sub; ++j) {
-      const int32_t* cns = sched ? sched->cn_list + (size_t)j * sched->width : nullptr;
+      const int32_t* cns = sched ? sched->cn_list.get() + (size_t)j * sched->width : nullptr;
       const int n_cns = sched ? sched->width : g->num_cn;
       launch_cn64(cn_mode, dim3(gx, ygrid(n_cns)), st, msg, xtot, g, cns, n_cns, batch, from_state ? 1 : 0, llr_max, offset);
       if (from_state && sched)
-        hipLaunchKernelGGL(zero_inactive64_kernel, dim3(gx, ygrid(g->num_cn)), dim3(64), 0, st, msg, g->cn_ptr, g->cn_edge,
-                           sched->first_mask, g->num_cn, batch);
+        hipLaunchKernelGGL(zero_inactive64_kernel, dim3(gx, ygrid(g->num_cn)), dim3(64), 0, st, msg, g->cn_ptr.get(),
+                           g->cn_edge.get(), sched->first_mask.get(), g->num_cn, batch);
       from_state = false;
-      const int32_t* vns = sched ? sched->vn_list + sched->vn_off[j] : nullptr;
+      const int32_t* vns = sched ? sched->vn_list.get() + sched->vn_off[j] : nullptr;
       const int n_vns = sched ? sched->vn_off[j + 1] - sched->vn_off[j] : g->num_vn;
-      hipLaunchKernelGGL(vn_total64_kernel, dim3(gx, ygrid(n_vns)), dim3(64), 0, st, msg, llr_t, xtot, g->vn_ptr, vns, n_vns, batch);
+      hipLaunchKernelGGL(vn_total64_kernel, dim3(gx, ygrid(n_vns)), dim3(64), 0, st, msg, llr_t, xtot, g->vn_ptr.get(), vns,
+                         n_vns, batch);
     }
   hipLaunchKernelGGL(finish64_kernel, dim3(gx, ygrid(out_cols)), dim3(64), 0, st, xtot, out, batch, out_cols, hard_out, llr_max);
   if (state_out && !(num_iter == 0 && state_in))
-    hipLaunchKernelGGL(v2c_state64_kernel, dim3(gx, ygrid(g->num_vn)), dim3(64), 0, st, msg, xtot, g->vn_ptr, state, g->num_vn,
-                       batch, llr_max);
+    hipLaunchKernelGGL(v2c_state64_kernel, dim3(gx, ygrid(g->num_vn)), dim3(64), 0, st, msg, xtot, g->vn_ptr.get(), state,
+                       g->num_vn, batch, llr_max);
   return launch_status();
 }
 

@@ -1,4 +1,5 @@
-// Shared declarations of the 5G-NR QC-LDPC kernels (handle layout, rate-matching index maps).
+// Shared declarations of the 5G-NR QC-LDPC kernels: the handle (code parameters + one table struct per engine, each next to
+// that engine's functions), the schedulers the table builders share, and the rate-matching index maps.
 #pragma once
 #include "common.h"
 #include "options.h"
@@ -14,7 +15,7 @@
 struct samd_ldpc5g_opt {
   bool enc_bytes = false, enc_persist = false, onchip_compressed = false, force_spill = false, no_spill = false;
   bool no_onchip_layered = false, bp_engine = false, onchip_v1 = false, ms_nogroup = false, ms_noz128 = false;
-  int ms_var = 1, ms_ldsbar = 0, onchip_grid = 0, enc_dbg = 0, ms_dataflow = 0;
+  int ms_var = 1, ms_ldsbar = 0, onchip_grid = 0, enc_dbg = 0;
   // boxplus-phi on the generated kernel (bit-identical).  Round 5, loops unrolled: SLOWER than the generic explicit-message
   // kernel (437 KB of code for 16 wave programs, 1076 spilled registers: 144.7 against 119.9 ms per 65536 C2 codewords).
   // Round 6, check-node loops rolled (jit_cn_phi_rolled): 113.0 ms at C2 (0.580 M against 0.546 M decodes/s), 1.5 - 2 x the
@@ -36,7 +37,6 @@ struct samd_ldpc5g_opt {
     ms_nogroup = opt_set("SAMD_MS_NOGROUP"); ms_noz128 = opt_set("SAMD_MS_NOZ128");
     ms_var = (int)opt_int("SAMD_MS_VAR", 1) & 1; ms_ldsbar = (int)opt_int("SAMD_MS_LDSBAR", 0);
     onchip_grid = (int)opt_int("SAMD_ONCHIP_GRID", 0);
-    ms_dataflow = (int)opt_int("SAMD_MS_DATAFLOW", 0);
     jit_phi = (int)opt_int("SAMD_LDPC_JIT_PHI", -1);
     jit = (int)opt_int("SAMD_LDPC_JIT", 1); jit_min_batch = (int)opt_int("SAMD_LDPC_JIT_MIN_BATCH", 256);
 #ifdef SAMD_DEV
@@ -46,105 +46,121 @@ struct samd_ldpc5g_opt {
 };
 
 namespace samd { struct JitPlan; struct JitState; }
+struct samd_ldpc5g;
+
+// One struct per decoder engine: its scalars and the device tables it owns (DeviceTable, common.h - freed with the handle).
+// A builder fills its own struct only and reads the handle's code parameters; the order of engines a decode tries is
+// decode_engines() in ldpc5g.hip, the one statement of that policy.
+namespace samd {
+typedef std::vector<std::vector<std::pair<int, int>>> BaseRows;   // per base row: (column, shift mod Z), ascending column
+constexpr int kRowStride = 20;   // max row degree of BG1 is 19
+constexpr int kColStride = 32;   // max column degree of BG1 is 30
+constexpr int kDecWaves = 16;    // waves of one CU's decoder workgroups (1 x 16, 2 x 8 or 4 x 4)
+
+// ---- base graph, encoder map and the work items of the first on-chip kernel (ldpc5g.hip)
+struct Ldpc5gBase {
+  DeviceTable<int32_t> row_ptr;  // [mb+1]  CSR by row (entries ascending column)
+  DeviceTable<int32_t> row_ent;  // [nnz]   col | shift<<16   (shift already mod Z)
+  DeviceTable<int32_t> col_ptr;  // [nb+1]  CSC by column (entries ascending row)
+  DeviceTable<int32_t> col_ent;  // [nnz]   row | shift<<8 | pos<<20  (pos = index of the edge inside its row)
+  DeviceTable<uint16_t> enc_out_idx;   // [n] bit-packed encoder (Z % 32 == 0): output position -> position in the full codeword
+  DeviceTable<int32_t> cn_items, vn_items;   // work items for the decoder, longest first: (index | chunk<<16)
+  int n_cn_items = 0, n_vn_items = 0;
+};
+
+// ---- statically scheduled compressed-state decoder (ldpc5g_onchip.hip)
+struct Ldpc5gV2 {
+  int ok = 0;                  // all row degrees have an unrolled instantiation
+  int ncu = 0, nbu = 0;        // base rows / columns that hold at least one un-pruned node
+  int dec_waves = 16;          // waves per workgroup (16 / 8 / 4: small codes share a CU)
+  int llr_global = 0;          // 1: channel LLRs in the caller's workspace (L2) instead of LDS (larger codes fit)
+  DeviceTable<int32_t> row_pad;  // [mb*20]  (c*z) | shift<<16, entries ascending column
+  DeviceTable<int32_t> row_deg;  // [mb]
+  DeviceTable<int32_t> col_pad;  // [nb*32]  (r*z) | shift<<16 | pos<<25, padded with the zero dummy CN block
+  DeviceTable<int32_t> col_cls;  // [nb]     unrolled class size (>= column degree)
+  DeviceTable<int32_t> cn_sched_ptr, cn_sched, vn_sched_ptr, vn_sched;   // per-wave item lists (LPT balanced)
+};
+int build_onchip_tables(samd_ldpc5g* h, const BaseRows& by_row);
+size_t onchip_workspace_bytes(const samd_ldpc5g* h, int batch);
+int launch_onchip_v2(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
+                     float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
+                     size_t workspace_bytes, hipStream_t st);
+
+// ---- first boxplus / boxplus-phi engine (ldpc5g_onchip_bp.hip): one float per edge in LDS
+struct Ldpc5gBp {
+  int ok = 0, waves = 16, llr_global = 0, edges = 0;   // edges: base-graph edges of the used rows
+  DeviceTable<int32_t> row_off;   // [mb]     byte offset of the row's first edge block (blocks are Z floats) | degree << 18
+  DeviceTable<int32_t> col_ent;   // [nb*32]  (edge block byte offset) | (4*shift) << 18, rows ascending
+  DeviceTable<int32_t> col_deg;   // [nb]
+  DeviceTable<int32_t> cn_ptr, cn_list, vn_ptr, vn_list;   // per-wave item lists (LPT balanced)
+};
+// ---- explicit-message engine (ldpc5g_onchip_ms.*) on the same message layout (bp.edges, bp.waves, bp.llr_global):
+// compact edge tables + self-contained list entries
+struct Ldpc5gMs {
+  DeviceTable<int32_t> col_ent;   // [2 E + pad] per column, rows ascending: edge block byte offset, 4*shift
+  DeviceTable<int32_t> cn_ptr, vn_ptr;   // per-wave list offsets (VN: per-iteration lists, then fused columns)
+  DeviceTable<int32_t> cn_list;   // [2 items]  row block byte offset | (degree | fused<<5)<<18,  r | chunk<<8 | fused column<<16
+  DeviceTable<int32_t> vn_list;   // [2 items]  c | chunk<<8 | degree<<16,  dword offset into col_ent
+  DeviceTable<int32_t> tail_tab;  // [2 x groups] packed-tail items: row block byte offset, r | fused column<<16 (r = 0xFF: no row)
+  int tail_sh = 6;                // log2 of the lane-group width of a packed-tail item
+  DeviceTable<int32_t> vtail_tab; // [2 x groups] packed-tail VN items: dword offset of the column's edge table, c (0xFF: no column)
+  // grouped dispatch of the same items (ldpc5g_decode_msg_kernel): items of a wave sorted by body type
+  int g_ok = 0;
+  DeviceTable<int32_t> g_ptr;     // [2 (NW+1)] group offsets per wave: CN groups, then VN groups
+  DeviceTable<int32_t> g_cn, g_vn;   // [2 groups] body type, first item | (last + 1) << 16
+  DeviceTable<int32_t> i_cn, i_vn;   // [2 items]  see ldpc5g_onchip_ms.inc
+};
+// One builder fills Ldpc5gBp and Ldpc5gMs: the explicit-message lists are derived from the boxplus engine's row offsets,
+// column tables and LPT item costs, intermediates of the same pass (ldpc5g_onchip_bp.hip).
+int build_onchip_bp_tables(samd_ldpc5g* h, const BaseRows& by_row);
+size_t onchip_bp_workspace_bytes(const samd_ldpc5g* h, int batch);
+size_t onchip_bp_lds_bytes(const samd_ldpc5g* h);
+int onchip_bp_grid(const samd_ldpc5g* h, int batch);
+int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
+                     float llr_max, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes,
+                     hipStream_t st);
+int launch_onchip_ms(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
+                     float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
+                     size_t workspace_bytes, hipStream_t st);
+
+// ---- explicit-message engine with the last rows' messages in the L2 workspace row (ldpc5g_onchip_mss.hip)
+struct Ldpc5gSpill {
+  int ok = 0, lds_bytes = 0, g_floats = 0, spill_pct = 0;   // spill_pct: share of the edges in L2
+  DeviceTable<int32_t> col_ent, cn_ptr, vn_ptr, cn_list, vn_list;
+};
+int build_onchip_mss_tables(samd_ldpc5g* h, const BaseRows& by_row);
+size_t onchip_mss_workspace_bytes(const samd_ldpc5g* h, int batch);
+int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
+                      float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
+                      size_t workspace_bytes, hipStream_t st);
+
+// ---- on-chip layered decoder (ldpc5g_onchip_ly.hip): record lists per wave, row / column edge tables
+struct Ldpc5gLayered {
+  int ok = 0, lds_bytes = 0, msg_floats = 0, n_ext = 0, groups = 0, zero_off = 0, waves = 16, bp_lds_bytes = 0;
+  DeviceTable<int32_t> rec_ptr, recs, ent_tab, xt_index, slot_tab, bp_rec_ptr, bp_recs, bp_slot_tab;
+};
+int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row);
+size_t onchip_ly_workspace_bytes(const samd_ldpc5g* h, int batch);
+int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode, float llr_max,
+                     float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes, hipStream_t st);
+}  // namespace samd
 
 struct samd_ldpc5g {
   samd_ldpc5g_opt opt;
   int host_only = 0;           // built without a device (SAMD_HOST_ONLY): tables and schedules only, no launch
   samd::JitPlan* jit_plan = nullptr;     // schedule of the specialised kernel (ldpc5g_jit.h); null: code outside its class
-  samd::JitState* jit_state = nullptr;   // compiled modules, created lazily (mutable behind a const handle)
+  samd::JitState* jit_state = nullptr;   // compiled modules, created lazily (mutable behind a const handle); both: free_jit
   int bg = 0, z = 0, k = 0, n = 0, m_int = 0, nb_pruned = 0;
   int mb = 0, nb = 0, k_b = 0, k_ldpc = 0, n_ldpc = 0, n_vn = 0, n_cn = 0;
   int s_a = 0, s_b = 0;  // shifts of the core entries P_A, P_B (encoding.py:476-481)
   int nnz = 0, max_dc = 0, max_dv = 0;
-  // base graph, CSR by row (entries ascending column) - device
-  int32_t* row_ptr = nullptr;  // [mb+1]
-  int32_t* row_ent = nullptr;  // [nnz]  col | shift<<16   (shift already mod Z)
-  // base graph, CSC by column (entries ascending row) - device
-  int32_t* col_ptr = nullptr;  // [nb+1]
-  int32_t* col_ent = nullptr;  // [nnz]  row | shift<<8 | pos<<20  (pos = index of the edge inside its row)
-  // work items for the decoder, longest first: (index | chunk<<16)
-  uint16_t* enc_out_idx = nullptr;   // [n] bit-packed encoder (Z % 32 == 0): output position -> position in the full codeword
-  int32_t* cn_items = nullptr; int n_cn_items = 0;
-  int32_t* vn_items = nullptr; int n_vn_items = 0;
-  // ---- tables of the statically scheduled on-chip decoder (csrc/ldpc5g_onchip.hip)
-  int v2_ok = 0;               // all row degrees have an unrolled instantiation
-  int ncu = 0, nbu = 0;        // base rows / columns that hold at least one un-pruned node
-  int32_t* row_pad = nullptr;  // [mb*20]  (c*z) | shift<<16, entries ascending column
-  int32_t* row_deg = nullptr;  // [mb]
-  int32_t* col_pad = nullptr;  // [nb*32]  (r*z) | shift<<16 | pos<<25, padded with the zero dummy CN block
-  int32_t* col_cls = nullptr;  // [nb]     unrolled class size (>= column degree)
-  int32_t* cn_sched_ptr = nullptr; int32_t* cn_sched = nullptr;   // per-wave item lists (LPT balanced)
-  int32_t* vn_sched_ptr = nullptr; int32_t* vn_sched = nullptr;
-  // ---- on-chip boxplus / boxplus-phi engine (csrc/ldpc5g_onchip_bp.hip): one float per edge in LDS
-  int bp_ok = 0, bp_waves = 16, bp_llr_global = 0, bp_edges = 0;   // bp_edges: base-graph edges of the used rows
-  int32_t* bp_row_off = nullptr;   // [mb]     byte offset of the row's first edge block (blocks are Z floats) | degree << 18
-  int32_t* bp_col_ent = nullptr;   // [nb*32]  (edge block byte offset) | (4*shift) << 18, rows ascending
-  // explicit-message min-sum engine (ldpc5g_onchip_ms.hip): compact edge tables + self-contained list entries
-  int32_t* ms_col_ent = nullptr;   // [2 E + pad] per column, rows ascending: edge block byte offset, 4*shift
-  int32_t* ms_cn_ptr = nullptr; int32_t* ms_vn_ptr = nullptr;   // per-wave list offsets (VN: per-iteration lists, then fused columns)
-  int32_t* ms_cn_list = nullptr;   // [2 items]  row block byte offset | (degree | fused<<5)<<18,  r | chunk<<8 | fused column<<16
-  int32_t* ms_vn_list = nullptr;   // [2 items]  c | chunk<<8 | degree<<16,  dword offset into ms_col_ent
-  int32_t* ms_tail_tab = nullptr;  // [2 x groups] packed-tail items: row block byte offset, r | fused column<<16 (r = 0xFF: no row)
-  int ms_tail_sh = 6;              // log2 of the lane-group width of a packed-tail item
-  int32_t* ms_vtail_tab = nullptr; // [2 x groups] packed-tail VN items: dword offset of the column's edge table, c (0xFF: no column)
-  // grouped dispatch of the same items (ldpc5g_decode_msg_kernel): items of a wave sorted by body type
-  int ms_g_ok = 0;
-  int32_t* ms_g_ptr = nullptr;     // [2 (NW+1)] group offsets per wave: CN groups, then VN groups
-  int32_t* ms_g_cn = nullptr; int32_t* ms_g_vn = nullptr;   // [2 groups] body type, first item | (last + 1) << 16
-  int32_t* ms_i_cn = nullptr; int32_t* ms_i_vn = nullptr;   // [2 items]  see ldpc5g_onchip_ms.inc
-  int ms_df_ok = 0;                // dataflow readiness instead of the two barriers per iteration (SAMD_MS_DATAFLOW)
-  int32_t* ms_d_cn = nullptr; int32_t* ms_d_vn = nullptr;   // [4 items]  need mask lo / hi, own counter byte offset, increment
-  int32_t* bp_col_deg = nullptr;   // [nb]
-  int32_t* bp_cn_ptr = nullptr; int32_t* bp_cn_list = nullptr;     // per-wave item lists (LPT balanced)
-  int32_t* bp_vn_ptr = nullptr; int32_t* bp_vn_list = nullptr;
-  // explicit-message min-sum engine with the last rows' messages in the L2 workspace row (ldpc5g_onchip_mss.hip)
-  int sp_ok = 0, sp_lds_bytes = 0, sp_g_floats = 0, sp_spill_pct = 0;   // sp_spill_pct: share of the edges in L2
-  int32_t* sp_col_ent = nullptr; int32_t* sp_cn_ptr = nullptr; int32_t* sp_vn_ptr = nullptr;
-  int32_t* sp_cn_list = nullptr; int32_t* sp_vn_list = nullptr;
-  // on-chip layered decoder (ldpc5g_onchip_ly.hip): record lists per wave, row / column edge tables
-  int ly_ok = 0, ly_lds_bytes = 0, ly_msg_floats = 0, ly_n_ext = 0, ly_groups = 0, ly_zero_off = 0, ly_waves = 16;
-  int32_t* ly_rec_ptr = nullptr; int32_t* ly_recs = nullptr; int32_t* ly_ent_tab = nullptr;
-  int32_t* ly_xt_index = nullptr; int32_t* ly_slot_tab = nullptr;
-  int32_t* ly_bp_rec_ptr = nullptr; int32_t* ly_bp_recs = nullptr; int32_t* ly_bp_slot_tab = nullptr; int ly_bp_lds_bytes = 0;
-  int dec_waves = 16;          // waves per workgroup of the on-chip decoder (16 / 8 / 4: small codes share a CU)
-  int llr_global = 0;          // 1: channel LLRs in the caller's workspace (L2) instead of LDS (larger codes fit)
+  samd::Ldpc5gBase base;
+  samd::Ldpc5gV2 v2;
+  samd::Ldpc5gBp bp;
+  samd::Ldpc5gMs ms;
+  samd::Ldpc5gSpill sp;
+  samd::Ldpc5gLayered ly;
 };
-
-namespace samd {
-constexpr int kRowStride = 20;   // max row degree of BG1 is 19
-constexpr int kColStride = 32;   // max column degree of BG1 is 30
-constexpr int kDecWaves = 16;    // waves of one CU's decoder workgroups (1 x 16, 2 x 8 or 4 x 4)
-// build the v2 tables (host); defined in ldpc5g_onchip.hip
-int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
-void free_onchip_tables(samd_ldpc5g* h);
-size_t onchip_workspace_bytes(const samd_ldpc5g* h, int batch);
-int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
-void free_onchip_bp_tables(samd_ldpc5g* h);
-size_t onchip_bp_workspace_bytes(const samd_ldpc5g* h, int batch);
-size_t onchip_bp_lds_bytes(const samd_ldpc5g* h);
-int onchip_bp_grid(const samd_ldpc5g* h, int batch);
-// explicit-message min-sum engine (ldpc5g_onchip_ms.hip), same tables as the boxplus engine
-int launch_onchip_ms(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
-                     float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
-                     size_t workspace_bytes, hipStream_t st);
-int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
-                     float llr_max, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes,
-                     hipStream_t st);
-int build_onchip_mss_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
-void free_onchip_mss_tables(samd_ldpc5g* h);
-size_t onchip_mss_workspace_bytes(const samd_ldpc5g* h, int batch);
-int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
-                      float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
-                      size_t workspace_bytes, hipStream_t st);
-int build_onchip_ly_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
-void free_onchip_ly_tables(samd_ldpc5g* h);
-size_t onchip_ly_workspace_bytes(const samd_ldpc5g* h, int batch);
-int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode, float llr_max,
-                     float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes, hipStream_t st);
-int launch_onchip_v2(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
-                     float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
-                     size_t workspace_bytes, hipStream_t st);
-}
 
 namespace samd {
 

@@ -386,7 +386,7 @@ extern "C" int samd_ldpc5g_create(int bg, int z, const int16_t* rows, const int1
   const bool ok = k > 0 && k <= h->k_ldpc && n > 0 && nb_pruned >= 0 && h->n_cn > 0 &&
                   2 * z + n <= h->n_vn - (h->k_ldpc - k) && (num_bits_per_symbol <= 0 || n % num_bits_per_symbol == 0);
   if (!ok) { delete h; set_error("inconsistent 5G LDPC parameters"); return SAMD_ERR_INVALID; }
-  std::vector<std::vector<std::pair<int, int>>> by_row(h->mb), by_col(h->nb);
+  BaseRows by_row(h->mb), by_col(h->nb);
   for (int e = 0; e < num_entries; ++e) {
     const int r = rows[e], c = cols[e];
     if (r < 0 || r >= h->mb || c < 0 || c >= h->nb || shifts[e] < 0) { delete h; set_error("bad base-graph entry"); return SAMD_ERR_INVALID; }
@@ -429,13 +429,13 @@ extern "C" int samd_ldpc5g_create(int bg, int z, const int16_t* rows, const int1
   std::vector<int32_t> cn_items, vn_items;
   for (auto& x : ci) cn_items.push_back(x.second);
   for (auto& x : vi) vn_items.push_back(x.second);
-  h->n_cn_items = (int)cn_items.size(); h->n_vn_items = (int)vn_items.size();
-  int rc = upload(&h->row_ptr, row_ptr.data(), row_ptr.size());
-  if (rc == SAMD_OK) rc = upload(&h->row_ent, row_ent.data(), row_ent.size());
-  if (rc == SAMD_OK) rc = upload(&h->col_ptr, col_ptr.data(), col_ptr.size());
-  if (rc == SAMD_OK) rc = upload(&h->col_ent, col_ent.data(), col_ent.size());
-  if (rc == SAMD_OK) rc = upload(&h->cn_items, cn_items.data(), cn_items.size());
-  if (rc == SAMD_OK) rc = upload(&h->vn_items, vn_items.data(), vn_items.size());
+  h->base.n_cn_items = (int)cn_items.size(); h->base.n_vn_items = (int)vn_items.size();
+  int rc = h->base.row_ptr.assign(row_ptr);
+  if (rc == SAMD_OK) rc = h->base.row_ent.assign(row_ent);
+  if (rc == SAMD_OK) rc = h->base.col_ptr.assign(col_ptr);
+  if (rc == SAMD_OK) rc = h->base.col_ent.assign(col_ent);
+  if (rc == SAMD_OK) rc = h->base.cn_items.assign(cn_items);
+  if (rc == SAMD_OK) rc = h->base.vn_items.assign(vn_items);
   if (rc == SAMD_OK && z % 32 == 0 && h->n_ldpc < 65536) {
     // output position -> position in the full codeword (output interleaver and puncturing / filler removal folded)
     std::vector<uint16_t> oi(n + 2, 0);                    // (+ padding: the kernel copies the table in 32-bit words)
@@ -445,7 +445,7 @@ extern "C" int samd_ldpc5g_create(int bg, int z, const int16_t* rows, const int1
       const int uu = t + 2 * z;                                                // short_to_full
       oi[i] = (uint16_t)(uu < k ? uu : uu + (h->k_ldpc - k));
     }
-    rc = upload(&h->enc_out_idx, oi.data(), oi.size());
+    rc = h->base.enc_out_idx.assign(oi);
   }
   if (rc == SAMD_OK) rc = build_onchip_tables(h, by_row);
   if (rc == SAMD_OK) rc = build_onchip_bp_tables(h, by_row);
@@ -460,19 +460,13 @@ extern "C" int samd_ldpc5g_create(int bg, int z, const int16_t* rows, const int1
 
 extern "C" void samd_ldpc5g_destroy(samd_ldpc5g_t* h) {
   if (!h) return;
-  (void)hipFree(h->row_ptr); (void)hipFree(h->row_ent); (void)hipFree(h->col_ptr); (void)hipFree(h->col_ent);
-  (void)hipFree(h->cn_items); (void)hipFree(h->vn_items); (void)hipFree(h->enc_out_idx);
-  free_onchip_tables(h);
-  free_onchip_bp_tables(h);
-  free_onchip_mss_tables(h);
-  free_onchip_ly_tables(h);
   free_jit(h);
-  delete h;
+  delete h;                                                // every device table is freed by its engine struct
 }
 
 extern "C" int samd_ldpc5g_encode_f32(const samd_ldpc5g_t* h, const float* bits, float* out, int batch, void* stream) {
   SAMD_REQUIRE(h && bits && out && batch > 0, "bad argument");
-  if (h->enc_out_idx && h->z % 32 == 0 && !h->opt.enc_bytes) {
+  if (h->base.enc_out_idx.get() && h->z % 32 == 0 && !h->opt.enc_bytes) {
     // lifting sizes that are multiples of 32: the bit-packed kernel, one wave per codeword
     const int wq = h->z / 32;
     const size_t lds_p = (4 * (size_t)((h->mb + h->k_b) * wq + 4 * wq) + (size_t)h->mb + 1 + (size_t)h->nnz) * sizeof(uint32_t) +
@@ -483,14 +477,14 @@ extern "C" int samd_ldpc5g_encode_f32(const samd_ldpc5g_t* h, const float* bits,
     // against 0.28 ms (input + rows) + 0.42 ms (output) for the separate phases at C2
     const int grid = h->opt.enc_persist ? std::min((batch + 3) / 4, 256 * 8 * 4) : (batch + 3) / 4;
     hipLaunchKernelGGL(ldpc5g_encode_packed_kernel, dim3(grid), dim3(256), lds_p, (hipStream_t)stream, bits, out, make_rm(h),
-                       batch, h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->row_ptr, h->row_ent, h->enc_out_idx,
-                       h->opt.enc_dbg);
+                       batch, h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->base.row_ptr.get(), h->base.row_ent.get(),
+                       h->base.enc_out_idx.get(), h->opt.enc_dbg);
     return launch_status();
   }
   const size_t lds = (size_t)h->n_ldpc + 4 * (size_t)h->z;
   SAMD_SET_MAX_LDS(ldpc5g_encode_kernel, 64 * 1024);
   hipLaunchKernelGGL(ldpc5g_encode_kernel, dim3(batch), dim3(256), lds, (hipStream_t)stream, bits, out, make_rm(h),
-                     h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->row_ptr, h->row_ent);
+                     h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->base.row_ptr.get(), h->base.row_ent.get());
   return launch_status();
 }
 
@@ -516,38 +510,73 @@ extern "C" int samd_ldpc5g_extract_codeword_f32(const samd_ldpc5g_t* h, const fl
   return launch_status();
 }
 
-// min-sum family: explicit messages (ldpc5g_onchip_ms.hip) when they fit in LDS, else the compressed
-// check-node state (ldpc5g_onchip.hip, every 5G code).  SAMD_ONCHIP_COMPRESSED=1 forces the latter.
-static bool use_explicit_minsum(const samd_ldpc5g* h) { return h->bp_ok && h->ms_cn_list && h->ms_vn_list && !h->opt.onchip_compressed; }
-// ... or explicit messages with the last base rows' blocks in the L2 workspace row (ldpc5g_onchip_mss.hip)
-// measured (tools/sweep_ldpc.py): up to about a quarter of the edges in L2 this beats the compressed state engine
-// (+16 % at 4 %, +9 % at 26 %, even at 28 %); beyond that the L2 round trips of the VN phase dominate
-static bool use_spill_minsum(const samd_ldpc5g* h) {
-  return !h->bp_ok && h->sp_ok && (h->sp_spill_pct <= 27 || h->opt.force_spill) &&
-         !h->opt.onchip_compressed && !h->opt.no_spill;
+// ---- engine selection: decode_engines() is the ONE statement of which engines a decode tries and in what order; the
+// launch, the workspace query and samd_ldpc5g_decode_engine all read it.
+enum Engine { kEngFirst, kEngV2, kEngBp, kEngMs, kEngSpill, kEngJit, kEngCount };
+struct EngineList {
+  int n = 0;
+  Engine e[kEngCount];                                     // an engine appears at most once: room for all of them
+  void add(Engine x) { if (n < kEngCount) e[n++] = x; }
+};
+static bool is_boxplus(int cn_mode) {
+  return cn_mode == SAMD_CN_BOXPLUS || cn_mode == SAMD_CN_BOXPLUS_PHI || cn_mode == SAMD_CN_BOXPLUS_PHI_FAST;
 }
-// boxplus rules on codes whose messages exceed LDS: the alternative is the HBM-resident engine, and the phi / tanh
-// arithmetic (VALU bound) hides the L2 round trips - any spill share
-static bool use_spill_boxplus(const samd_ldpc5g* h) { return !h->bp_ok && h->sp_ok && !h->opt.no_spill; }
+// Every other cn_mode counts as the min-sum family here: the callers reject unknown modes.  An engine that answers
+// SAMD_ERR_UNSUPPORTED hands over to the next of the list.  (SAMD_ONCHIP_V1 is no part of the choice: it makes the
+// launch pass over kEngV2, and the two queries have always answered without it.)
+static EngineList decode_engines(const samd_ldpc5g* h, int cn_mode) {
+  EngineList l;
+  // explicit messages (ldpc5g_onchip_ms.hip) when they fit in LDS; SAMD_ONCHIP_COMPRESSED=1 forces the compressed state
+  const bool explicit_ms = h->bp.ok && h->ms.cn_list.get() && h->ms.vn_list.get() && !h->opt.onchip_compressed;
+  // ... or with the last base rows' blocks in L2 (ldpc5g_onchip_mss.hip)
+  const bool spill = !h->bp.ok && h->sp.ok && !h->opt.no_spill;
+  if (is_boxplus(cn_mode)) {
+    // codes whose messages exceed LDS: the alternative is the HBM-resident engine, and the phi / tanh arithmetic (VALU
+    // bound) hides the L2 round trips - any spill share
+    if (spill) { l.add(kEngSpill); return l; }
+    // the explicit-message engine with the boxplus node update (pair items, fused degree-1 columns, prefetched
+    // descriptors); SAMD_BP_ENGINE=1 keeps the first boxplus kernel (ldpc5g_onchip_bp.hip) alone
+    if (explicit_ms && !h->opt.bp_engine) l.add(kEngMs);
+    l.add(kEngBp);
+    return l;
+  }
+  // min-sum: else the kernel generated for this code (ldpc5g_jit.cpp: any even lifting size whose messages fit LDS)
+  l.add(explicit_ms ? kEngMs : kEngJit);
+  // measured (tools/sweep_ldpc.py): up to about a quarter of the edges in L2 the spill engine beats the compressed state
+  // engine (+16 % at 4 %, +9 % at 26 %, even at 28 %); beyond that the L2 round trips of the VN phase dominate
+  if (spill && (h->sp.spill_pct <= 27 || h->opt.force_spill) && !h->opt.onchip_compressed) l.add(kEngSpill);
+  if (h->v2.ok) l.add(kEngV2);                             // statically scheduled, unrolled (every 5G code)
+  if (decode_lds_bytes(h) <= 160 * 1024) l.add(kEngFirst);
+  return l;
+}
+
+// the count-based duplicate-minimum test of the min-sum kernels equals the reference's 1e5-sentinel sum test only
+// while node_degree * 2 * llr_max stays below the sentinel (decoding.py:865-872)
+static bool minsum_envelope_ok(const samd_ldpc5g* h, float llr_max) {
+  return h->max_dc <= 27 && llr_max >= 0.f && !((double)h->max_dc * 2.0 * (double)llr_max >= 99999.0);
+}
 
 extern "C" size_t samd_ldpc5g_decode_workspace_bytes(const samd_ldpc5g_t* h, int batch, int cn_mode) {
   // 0 when the whole state fits in LDS; larger codes keep part of it in this (L2-resident) scratch
   if (!h) return 0;
-  const bool boxplus = cn_mode == SAMD_CN_BOXPLUS || cn_mode == SAMD_CN_BOXPLUS_PHI || cn_mode == SAMD_CN_BOXPLUS_PHI_FAST;
-  if (boxplus && use_spill_boxplus(h)) return onchip_mss_workspace_bytes(h, batch);
-  if (boxplus || use_explicit_minsum(h)) return onchip_bp_workspace_bytes(h, batch);
-  // (the kernel generated for a code beyond LDS keeps its last base rows' messages in a workspace row per workgroup; the
-  // generic engine behind it - the fall-back - has its own need: the larger of the two)
-  const size_t jw = jit_workspace_bytes(h, batch, cn_mode);
-  if (use_spill_minsum(h)) return std::max(jw, onchip_mss_workspace_bytes(h, batch));
-  return std::max(jw, onchip_workspace_bytes(h, batch));
+  // the need of the first engine of the list; the generated kernel's fall-back has its own: the larger of the two
+  size_t need = 0;
+  const EngineList l = decode_engines(h, cn_mode);
+  for (int i = 0; i < l.n; ++i) {
+    if (l.e[i] == kEngJit) { need = jit_workspace_bytes(h, batch, cn_mode); continue; }
+    if (l.e[i] == kEngSpill) return std::max(need, onchip_mss_workspace_bytes(h, batch));
+    if (l.e[i] == kEngMs || l.e[i] == kEngBp) return std::max(need, onchip_bp_workspace_bytes(h, batch));
+    if (l.e[i] == kEngV2) return std::max(need, onchip_workspace_bytes(h, batch));
+    break;                                                 // the first kernel needs none
+  }
+  return need;
 }
 
 // ---- layered schedule (one sub-iteration per base row) on chip: ldpc5g_onchip_ly.hip
 extern "C" int samd_ldpc5g_decode_layered_supported(const samd_ldpc5g_t* h, int cn_mode) {
   const bool rule = cn_mode == SAMD_CN_MINSUM || cn_mode == SAMD_CN_OFFSET_MINSUM || cn_mode == SAMD_CN_BOXPLUS_PHI ||
                     cn_mode == SAMD_CN_BOXPLUS_PHI_FAST;
-  return (h && h->ly_ok && rule && !h->opt.no_onchip_layered) ? 1 : 0;
+  return (h && h->ly.ok && rule && !h->opt.no_onchip_layered) ? 1 : 0;
 }
 
 extern "C" size_t samd_ldpc5g_decode_layered_workspace_bytes(const samd_ldpc5g_t* h, int batch) {
@@ -563,70 +592,21 @@ extern "C" int samd_ldpc5g_decode_layered_f32(const samd_ldpc5g_t* h, const floa
 }
 
 extern "C" int samd_ldpc5g_decode_engine(const samd_ldpc5g_t* h, int cn_mode) {
-  if (!h) return 0;
-  if (cn_mode == SAMD_CN_BOXPLUS || cn_mode == SAMD_CN_BOXPLUS_PHI || cn_mode == SAMD_CN_BOXPLUS_PHI_FAST)
-    return h->bp_ok ? 2 : (use_spill_boxplus(h) ? 3 : 0);
-  if (cn_mode != SAMD_CN_MINSUM && cn_mode != SAMD_CN_OFFSET_MINSUM) return 0;
-  if (use_explicit_minsum(h)) return 2;
-  if (use_spill_minsum(h)) return 3;
-  return (h->v2_ok || decode_lds_bytes(h) <= 160 * 1024) ? 1 : 0;
+  if (!h || !(is_boxplus(cn_mode) || cn_mode == SAMD_CN_MINSUM || cn_mode == SAMD_CN_OFFSET_MINSUM)) return 0;
+  // 1 compressed state, 2 messages in LDS, 3 messages spilled to L2, 0 none (the generated kernel reports its fall-back)
+  const EngineList l = decode_engines(h, cn_mode);
+  for (int i = 0; i < l.n; ++i) {
+    if (l.e[i] == kEngJit) continue;
+    if (l.e[i] == kEngBp) return h->bp.ok ? 2 : 0;
+    return l.e[i] == kEngMs ? 2 : l.e[i] == kEngSpill ? 3 : 1;
+  }
+  return 0;
 }
 
-extern "C" int samd_ldpc5g_decode_f32(const samd_ldpc5g_t* h, const float* llr, float* out, int batch, int num_iter,
-                                      int cn_mode, float llr_max, float offset, int hard_out, int return_infobits,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-  SAMD_REQUIRE(h && llr && out && batch > 0 && num_iter >= 0, "bad argument");
-  SAMD_REQUIRE(!h->host_only, "handle was built without a device (SAMD_HOST_ONLY)");
-  if (cn_mode == SAMD_CN_BOXPLUS || cn_mode == SAMD_CN_BOXPLUS_PHI || cn_mode == SAMD_CN_BOXPLUS_PHI_FAST) {   // one float per edge in LDS
-    SAMD_REQUIRE(llr_max >= 0.f, "bad argument");
-    if (use_spill_boxplus(h))                                             // ... the last rows' messages in L2
-      return launch_onchip_mss(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits,
-                               workspace, workspace_bytes, (hipStream_t)stream);
-    // the explicit-message engine with the boxplus node update (pair items, fused degree-1 columns, prefetched
-    // descriptors - ldpc5g_onchip_ms.hip); SAMD_BP_ENGINE=1 keeps the first boxplus kernel (ldpc5g_onchip_bp.hip)
-    if (use_explicit_minsum(h) && !h->opt.bp_engine) {
-      const int rc = launch_onchip_ms(h, llr, out, batch, num_iter, cn_mode, llr_max, 0.f, hard_out, return_infobits,
-                                      workspace, workspace_bytes, (hipStream_t)stream);
-      if (rc != SAMD_ERR_UNSUPPORTED) return rc;
-    }
-    // (the first boxplus kernel has the defined phi only: "fast" permits the hardware transcendentals, it does not demand them)
-    return launch_onchip_bp(h, llr, out, batch, num_iter, cn_mode == SAMD_CN_BOXPLUS_PHI_FAST ? SAMD_CN_BOXPLUS_PHI : cn_mode,
-                            llr_max, hard_out, return_infobits, workspace, workspace_bytes, (hipStream_t)stream);
-  }
-  if (cn_mode != SAMD_CN_MINSUM && cn_mode != SAMD_CN_OFFSET_MINSUM) {
-    set_error("unknown cn_mode");
-    return SAMD_ERR_UNSUPPORTED;
-  }
+// the first on-chip kernel: dynamic wave scheduler over the base graph's work items
+static int launch_onchip_first(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
+                               float llr_max, float offset, int hard_out, int return_infobits, hipStream_t stream) {
   const size_t lds = decode_lds_bytes(h);
-  // the count-based duplicate-minimum test equals the reference's 1e5-sentinel sum test only
-  // while node_degree * 2 * llr_max stays below the sentinel (decoding.py:865-872)
-  if (h->max_dc > 27 || !(llr_max >= 0.f) || (double)h->max_dc * 2.0 * (double)llr_max >= 99999.0) {
-    set_error("code / llr_max outside the on-chip decoder's envelope");
-    return SAMD_ERR_UNSUPPORTED;
-  }
-  if (use_explicit_minsum(h)) {
-    const int rc = launch_onchip_ms(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits,
-                                    workspace, workspace_bytes, (hipStream_t)stream);
-    if (rc != SAMD_ERR_UNSUPPORTED) return rc;
-  } else {
-    // the kernel generated for this code (ldpc5g_jit.cpp: any even lifting size whose messages fit LDS)
-    const int rc = launch_onchip_jit(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, workspace, workspace_bytes, stream);
-    if (rc != SAMD_ERR_UNSUPPORTED) return rc;
-  }
-  if (use_spill_minsum(h)) {
-    const int rc = launch_onchip_mss(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits,
-                                     workspace, workspace_bytes, (hipStream_t)stream);
-    if (rc != SAMD_ERR_UNSUPPORTED) return rc;
-  }
-  if (h->v2_ok && !h->opt.onchip_v1) {   // statically scheduled, unrolled engine
-    const int rc = launch_onchip_v2(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out,
-                                    return_infobits, workspace, workspace_bytes, (hipStream_t)stream);
-    if (rc != SAMD_ERR_UNSUPPORTED) return rc;
-  }
-  if (lds > 160 * 1024) {
-    set_error("code does not fit in LDS");
-    return SAMD_ERR_UNSUPPORTED;
-  }
   const bool off = (cn_mode == SAMD_CN_OFFSET_MINSUM);
   const void* fn = off ? (const void*)ldpc5g_decode_kernel<true> : (const void*)ldpc5g_decode_kernel<false>;
   SAMD_SET_MAX_LDS(fn, 160 * 1024);
@@ -637,9 +617,63 @@ extern "C" int samd_ldpc5g_decode_f32(const samd_ldpc5g_t* h, const float* llr, 
   const int grid = (int)std::min<size_t>((size_t)batch, (size_t)cus * std::min<size_t>(per_cu, 2));
   const float off_v = off ? offset : 0.f;
 #define SAMD_DEC_ARGS llr, out, make_rm(h), h->n_cn, batch, num_iter, llr_max, off_v, hard_out, return_infobits, \
-                      h->row_ptr, h->row_ent, h->col_ptr, h->col_ent, h->cn_items, h->n_cn_items, h->vn_items, h->n_vn_items
-  if (off) hipLaunchKernelGGL(ldpc5g_decode_kernel<true>, dim3(grid), dim3(kDecThreads), lds, (hipStream_t)stream, SAMD_DEC_ARGS);
-  else hipLaunchKernelGGL(ldpc5g_decode_kernel<false>, dim3(grid), dim3(kDecThreads), lds, (hipStream_t)stream, SAMD_DEC_ARGS);
+                      h->base.row_ptr.get(), h->base.row_ent.get(), h->base.col_ptr.get(), h->base.col_ent.get(), \
+                      h->base.cn_items.get(), h->base.n_cn_items, h->base.vn_items.get(), h->base.n_vn_items
+  if (off) hipLaunchKernelGGL(ldpc5g_decode_kernel<true>, dim3(grid), dim3(kDecThreads), lds, stream, SAMD_DEC_ARGS);
+  else hipLaunchKernelGGL(ldpc5g_decode_kernel<false>, dim3(grid), dim3(kDecThreads), lds, stream, SAMD_DEC_ARGS);
 #undef SAMD_DEC_ARGS
   return launch_status();
+}
+
+extern "C" int samd_ldpc5g_decode_f32(const samd_ldpc5g_t* h, const float* llr, float* out, int batch, int num_iter,
+                                      int cn_mode, float llr_max, float offset, int hard_out, int return_infobits,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  SAMD_REQUIRE(h && llr && out && batch > 0 && num_iter >= 0, "bad argument");
+  SAMD_REQUIRE(!h->host_only, "handle was built without a device (SAMD_HOST_ONLY)");
+  const bool boxplus = is_boxplus(cn_mode);
+  if (boxplus) {
+    SAMD_REQUIRE(llr_max >= 0.f, "bad argument");
+  } else if (cn_mode != SAMD_CN_MINSUM && cn_mode != SAMD_CN_OFFSET_MINSUM) {
+    set_error("unknown cn_mode");
+    return SAMD_ERR_UNSUPPORTED;
+  } else if (!minsum_envelope_ok(h, llr_max)) {
+    set_error("code / llr_max outside the on-chip decoder's envelope");
+    return SAMD_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const EngineList l = decode_engines(h, cn_mode);
+  for (int i = 0; i < l.n; ++i) {
+    int rc = SAMD_ERR_UNSUPPORTED;
+    switch (l.e[i]) {
+      case kEngJit:
+        rc = launch_onchip_jit(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, workspace,
+                               workspace_bytes, stream);
+        break;
+      case kEngMs:
+        rc = launch_onchip_ms(h, llr, out, batch, num_iter, cn_mode, llr_max, boxplus ? 0.f : offset, hard_out,
+                              return_infobits, workspace, workspace_bytes, st);
+        break;
+      case kEngBp:   // (the defined phi only: "fast" permits the hardware transcendentals, it does not demand them)
+        rc = launch_onchip_bp(h, llr, out, batch, num_iter,
+                              cn_mode == SAMD_CN_BOXPLUS_PHI_FAST ? SAMD_CN_BOXPLUS_PHI : cn_mode, llr_max, hard_out,
+                              return_infobits, workspace, workspace_bytes, st);
+        break;
+      case kEngSpill:
+        rc = launch_onchip_mss(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, workspace,
+                               workspace_bytes, st);
+        break;
+      case kEngV2:
+        if (h->opt.onchip_v1) break;                       // SAMD_ONCHIP_V1: straight to the first kernel
+        rc = launch_onchip_v2(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, workspace,
+                              workspace_bytes, st);
+        break;
+      case kEngFirst:
+        rc = launch_onchip_first(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, st);
+        break;
+      case kEngCount: break;
+    }
+    if (rc != SAMD_ERR_UNSUPPORTED) return rc;
+  }
+  if (!boxplus) set_error("code does not fit in LDS");    // (a boxplus engine has said why it declined)
+  return SAMD_ERR_UNSUPPORTED;
 }

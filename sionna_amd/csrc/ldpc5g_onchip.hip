@@ -321,28 +321,28 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_v2_kernel(
 static const int kCnDegrees[] = {3, 4, 5, 6, 7, 8, 9, 10, 19};
 static const int kVnRemClasses[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14};   // remainder after full chunks of 16
 
-int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row) {
+int build_onchip_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   const int z = h->z;
-  h->ncu = (h->n_cn + z - 1) / z;
-  h->nbu = (h->n_vn + z - 1) / z;
+  h->v2.ncu = (h->n_cn + z - 1) / z;
+  h->v2.nbu = (h->n_vn + z - 1) / z;
   // packed fields: byte offsets < 2^18, byte shifts < 2^11, row/col index < 256
-  bool ok = h->mb <= 255 && h->nb <= 255 && (h->ncu + 1) * z * 4 < (1 << 18) && h->nbu * z * 4 < (1 << 18);
+  bool ok = h->mb <= 255 && h->nb <= 255 && (h->v2.ncu + 1) * z * 4 < (1 << 18) && h->v2.nbu * z * 4 < (1 << 18);
   std::vector<int32_t> row_pad((size_t)h->mb * kRowStride, 0), row_deg(h->mb, 0);
   std::vector<std::vector<std::pair<int32_t, int32_t>>> cols(h->nb);
   for (int r = 0; r < h->mb && ok; ++r) {
     const int d = (int)by_row[r].size();
     row_deg[r] = d;
-    if (r < h->ncu && std::find(std::begin(kCnDegrees), std::end(kCnDegrees), d) == std::end(kCnDegrees)) ok = false;
+    if (r < h->v2.ncu && std::find(std::begin(kCnDegrees), std::end(kCnDegrees), d) == std::end(kCnDegrees)) ok = false;
     if (d > kRowStride) { ok = false; break; }
     for (int i = 0; i < d; ++i) {
       const int c = by_row[r][i].first, s = by_row[r][i].second;
       row_pad[(size_t)r * kRowStride + i] = (c * z * 4) | ((s * 4) << 18);
-      if (r < h->ncu) cols[c].push_back({(r * z * 4) | ((s * 4) << 18), i});   // rows ascending
+      if (r < h->v2.ncu) cols[c].push_back({(r * z * 4) | ((s * 4) << 18), i});   // rows ascending
     }
   }
   // column tables: 2 dwords per slot, full chunks of 16 slots then a remainder class
   std::vector<int32_t> col_pad((size_t)h->nb * 2 * kColStride, 0), col_cls(h->nb, 0);
-  const int32_t dummy = h->ncu * z * 4;                       // zero "dummy check node" block, shift 0
+  const int32_t dummy = h->v2.ncu * z * 4;                       // zero "dummy check node" block, shift 0
   for (int c = 0; c < h->nb && ok; ++c) {
     const int d = (int)cols[c].size();
     int nfull = d / 16;
@@ -357,14 +357,14 @@ int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<
       col_pad[((size_t)c * kColStride + i) * 2 + 1] = i < d ? cols[c][i].second : 0;
     }
   }
-  h->v2_ok = ok ? 1 : 0;
+  h->v2.ok = ok ? 1 : 0;
   if (!ok) return SAMD_OK;
   const int chunks = (z + 63) / 64;
-  if (chunks > 255) { h->v2_ok = 0; return SAMD_OK; }
+  if (chunks > 255) { h->v2.ok = 0; return SAMD_OK; }
   // rows whose last edge is the only edge of its column, with shift 0 and degree 3..10: that
   // degree-1 VN is handled inside the CN phase (cn_row<..., FUSE1>)
   std::vector<char> row_fused(h->mb, 0), col_fused(h->nb, 0);
-  for (int r = 0; r < h->ncu; ++r) {
+  for (int r = 0; r < h->v2.ncu; ++r) {
     const int d = row_deg[r];
     const int c = by_row[r][d - 1].first, s = by_row[r][d - 1].second;
     if (cols[c].size() == 1 && s == 0 && d >= 3 && d <= 10) { row_fused[r] = 1; col_fused[c] = 1; }
@@ -373,7 +373,7 @@ int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<
   // two consecutive fully valid 64-lane chunks of a row / column form one "pair" item (bit 25);
   // columns with >= 20 slots stay single-chunk items so that no item dwarfs a wave's fair share
   std::vector<std::pair<int, int32_t>> ci, vi, v1i;
-  for (int r = 0; r < h->ncu; ++r)
+  for (int r = 0; r < h->v2.ncu; ++r)
     for (int q = 0; q < chunks; ++q) {
       if (r * z + q * 64 >= h->n_cn) continue;
       const int32_t d0 = r | (q << 8) | (row_deg[r] << 16) | (row_fused[r] << 24);
@@ -381,7 +381,7 @@ int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<
       if (pair) { ci.push_back({2 * row_deg[r], d0 | (1 << 25)}); ++q; }
       else ci.push_back({row_deg[r], d0});
     }
-  for (int c = 0; c < h->nbu; ++c)
+  for (int c = 0; c < h->v2.nbu; ++c)
     for (int q = 0; q < chunks; ++q) {
       if (c * z + q * 64 >= h->n_vn) continue;
       const int nfull = col_cls[c] & 0xF, rem = col_cls[c] >> 4, slots = nfull * 16 + rem;
@@ -394,28 +394,28 @@ int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<
   // vn_sched_ptr = [16+1 offsets of the per-iteration lists | 16+1 offsets of the final degree-1 pass]
   std::vector<int32_t> cp, cl, vp, vl, v1p, v1l;
   // waves per workgroup from the LDS footprint: as many codewords per CU as fit, 16 waves in total
-  size_t lds = ((size_t)2 * h->nbu + (size_t)3 * (h->ncu + 1)) * z * 4;
-  h->llr_global = 0;
-  if (lds > 160 * 1024 && ((size_t)h->nbu + (size_t)3 * (h->ncu + 1)) * z * 4 <= 160 * 1024) {
-    h->llr_global = 1;                                          // channel LLRs move to the workspace (L2)
-    lds = ((size_t)h->nbu + (size_t)3 * (h->ncu + 1)) * z * 4;
-  } else if (lds > 160 * 1024 && (size_t)3 * (h->ncu + 1) * z * 4 <= 160 * 1024 && !opt_set("SAMD_NO_XTG")) {
-    h->llr_global = 2;                                          // x_tot as well: LDS = check-node state only
-    lds = (size_t)3 * (h->ncu + 1) * z * 4;
-  } else if (lds > 160 * 1024 && (size_t)2 * (h->ncu + 1) * z * 4 <= 160 * 1024 && !opt_set("SAMD_NO_XTG")) {
-    h->llr_global = 3;                                          // ... and the sign words: LDS = (M1, M2)
-    lds = (size_t)2 * (h->ncu + 1) * z * 4;
+  size_t lds = ((size_t)2 * h->v2.nbu + (size_t)3 * (h->v2.ncu + 1)) * z * 4;
+  h->v2.llr_global = 0;
+  if (lds > 160 * 1024 && ((size_t)h->v2.nbu + (size_t)3 * (h->v2.ncu + 1)) * z * 4 <= 160 * 1024) {
+    h->v2.llr_global = 1;                                          // channel LLRs move to the workspace (L2)
+    lds = ((size_t)h->v2.nbu + (size_t)3 * (h->v2.ncu + 1)) * z * 4;
+  } else if (lds > 160 * 1024 && (size_t)3 * (h->v2.ncu + 1) * z * 4 <= 160 * 1024 && !opt_set("SAMD_NO_XTG")) {
+    h->v2.llr_global = 2;                                          // x_tot as well: LDS = check-node state only
+    lds = (size_t)3 * (h->v2.ncu + 1) * z * 4;
+  } else if (lds > 160 * 1024 && (size_t)2 * (h->v2.ncu + 1) * z * 4 <= 160 * 1024 && !opt_set("SAMD_NO_XTG")) {
+    h->v2.llr_global = 3;                                          // ... and the sign words: LDS = (M1, M2)
+    lds = (size_t)2 * (h->v2.ncu + 1) * z * 4;
   }
-  h->dec_waves = 16;
+  h->v2.dec_waves = 16;
   for (int nwc : {8, 4, 2, 1})
-    if (lds * (size_t)(kDecWaves / nwc) <= 160 * 1024) h->dec_waves = nwc;
+    if (lds * (size_t)(kDecWaves / nwc) <= 160 * 1024) h->v2.dec_waves = nwc;
   if (opt_set("SAMD_ONCHIP_WAVES")) {
     const std::string e_s = opt_str("SAMD_ONCHIP_WAVES");
     const char* e = e_s.c_str();
     const int v = atoi(e);
-    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) h->dec_waves = v;      // experiments: force a workgroup size
+    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) h->v2.dec_waves = v;      // experiments: force a workgroup size
   }
-  const int nw = h->dec_waves;
+  const int nw = h->v2.dec_waves;
   lpt_schedule(ci, nw, &cp, &cl);
   lpt_schedule(vi, nw, &vp, &vl);
   {
@@ -427,39 +427,34 @@ int build_onchip_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<
   for (int32_t o : v1p) vp.push_back(o + (int32_t)vl.size());
   vl.insert(vl.end(), v1l.begin(), v1l.end());
   if (vl.empty()) vl.push_back(0);
-  int rc = upload(&h->row_pad, row_pad.data(), row_pad.size());
-  if (rc == SAMD_OK) rc = upload(&h->row_deg, row_deg.data(), row_deg.size());
-  if (rc == SAMD_OK) rc = upload(&h->col_pad, col_pad.data(), col_pad.size());
-  if (rc == SAMD_OK) rc = upload(&h->col_cls, col_cls.data(), col_cls.size());
-  if (rc == SAMD_OK) rc = upload(&h->cn_sched_ptr, cp.data(), cp.size());
-  if (rc == SAMD_OK) rc = upload(&h->cn_sched, cl.data(), cl.size());
-  if (rc == SAMD_OK) rc = upload(&h->vn_sched_ptr, vp.data(), vp.size());
-  if (rc == SAMD_OK) rc = upload(&h->vn_sched, vl.data(), vl.size());
+  int rc = h->v2.row_pad.assign(row_pad);
+  if (rc == SAMD_OK) rc = h->v2.row_deg.assign(row_deg);
+  if (rc == SAMD_OK) rc = h->v2.col_pad.assign(col_pad);
+  if (rc == SAMD_OK) rc = h->v2.col_cls.assign(col_cls);
+  if (rc == SAMD_OK) rc = h->v2.cn_sched_ptr.assign(cp);
+  if (rc == SAMD_OK) rc = h->v2.cn_sched.assign(cl);
+  if (rc == SAMD_OK) rc = h->v2.vn_sched_ptr.assign(vp);
+  if (rc == SAMD_OK) rc = h->v2.vn_sched.assign(vl);
   return rc;
-}
-
-void free_onchip_tables(samd_ldpc5g* h) {
-  (void)hipFree(h->row_pad); (void)hipFree(h->row_deg); (void)hipFree(h->col_pad); (void)hipFree(h->col_cls);
-  (void)hipFree(h->cn_sched_ptr); (void)hipFree(h->cn_sched); (void)hipFree(h->vn_sched_ptr); (void)hipFree(h->vn_sched);
 }
 
 // llr_global: 0 all in LDS; 1 LLRs in L2; 2 LLRs and x_tot in L2; 3 also the packed sign words (LDS = M1, M2)
 static size_t onchip_lds_bytes(const samd_ldpc5g* h) {
-  const int g = h->llr_global;
-  return ((size_t)(g >= 2 ? 0 : 2 - g) * h->nbu + (size_t)(g == 3 ? 2 : 3) * (h->ncu + 1)) * h->z * 4;
+  const int g = h->v2.llr_global;
+  return ((size_t)(g >= 2 ? 0 : 2 - g) * h->v2.nbu + (size_t)(g == 3 ? 2 : 3) * (h->v2.ncu + 1)) * h->z * 4;
 }
 
 static int onchip_grid(const samd_ldpc5g* h, int batch) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t per_cu = std::min<size_t>((size_t)(kDecWaves / h->dec_waves), std::max<size_t>(1, (160 * 1024) / onchip_lds_bytes(h)));
+  const size_t per_cu = std::min<size_t>((size_t)(kDecWaves / h->v2.dec_waves), std::max<size_t>(1, (160 * 1024) / onchip_lds_bytes(h)));
   return (int)std::min<size_t>((size_t)batch, (size_t)cus * per_cu);
 }
 
 size_t onchip_workspace_bytes(const samd_ldpc5g* h, int batch) {
-  if (!h->v2_ok || !h->llr_global || batch <= 0) return 0;
-  const size_t row = (size_t)std::min(h->llr_global, 2) * h->nbu * h->z + (h->llr_global == 3 ? (size_t)(h->ncu + 1) * h->z : 0);
+  if (!h->v2.ok || !h->v2.llr_global || batch <= 0) return 0;
+  const size_t row = (size_t)std::min(h->v2.llr_global, 2) * h->v2.nbu * h->z + (h->v2.llr_global == 3 ? (size_t)(h->v2.ncu + 1) * h->z : 0);
   return (size_t)onchip_grid(h, batch) * row * sizeof(float) + 256;
 }
 
@@ -472,7 +467,7 @@ int launch_onchip_v2(const samd_ldpc5g* h, const float* llr, float* out, int bat
     return SAMD_ERR_UNSUPPORTED;
   }
   float* llr_ws = nullptr;
-  if (h->llr_global) {
+  if (h->v2.llr_global) {
     if (!workspace || workspace_bytes < onchip_workspace_bytes(h, batch)) {
       set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
       return SAMD_ERR_WORKSPACE;
@@ -491,16 +486,18 @@ int launch_onchip_v2(const samd_ldpc5g* h, const float* llr, float* out, int bat
       ldpc5g_decode_v2_kernel<true, 1>,   ldpc5g_decode_v2_kernel<false, 16, true>, ldpc5g_decode_v2_kernel<true, 16, true>,
       ldpc5g_decode_v2_kernel<false, 16, true, true>, ldpc5g_decode_v2_kernel<true, 16, true, true>,
       ldpc5g_decode_v2_kernel<false, 16, true, true, true>, ldpc5g_decode_v2_kernel<true, 16, true, true, true>};
-  const int nw = h->dec_waves;
-  const int ki = h->llr_global ? 8 + 2 * h->llr_global + (pow2 ? 1 : 0)
+  const int nw = h->v2.dec_waves;
+  const int ki = h->v2.llr_global ? 8 + 2 * h->v2.llr_global + (pow2 ? 1 : 0)
                                : ((nw == 16 ? 0 : nw == 8 ? 2 : nw == 4 ? 4 : nw == 2 ? 6 : 8) | (pow2 ? 1 : 0));
   // set on every launch: the attribute is per device and a process may drive several
   SAMD_SET_MAX_LDS(kerns[ki], 160 * 1024);
   const int grid = onchip_grid(h, batch);
   const RateMatch rm = make_rate_match(h);
-  hipLaunchKernelGGL(kerns[ki], dim3(grid), dim3(nw * 64), lds, st, llr, out, llr_ws, rm, h->n_cn, h->ncu, h->nbu, batch,
-                     num_iter, llr_max, (off ? offset : 0.f), hard_out, return_infobits, h->row_pad, h->row_deg,
-                     h->col_pad, h->col_cls, h->cn_sched_ptr, h->cn_sched, h->vn_sched_ptr, h->vn_sched);
+  const samd::Ldpc5gV2& t = h->v2;
+  hipLaunchKernelGGL(kerns[ki], dim3(grid), dim3(nw * 64), lds, st, llr, out, llr_ws, rm, h->n_cn, t.ncu, t.nbu, batch,
+                     num_iter, llr_max, (off ? offset : 0.f), hard_out, return_infobits, t.row_pad.get(), t.row_deg.get(),
+                     t.col_pad.get(), t.col_cls.get(), t.cn_sched_ptr.get(), t.cn_sched.get(), t.vn_sched_ptr.get(),
+                     t.vn_sched.get());
   return launch_status();
 }
 

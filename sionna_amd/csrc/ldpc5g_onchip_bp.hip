@@ -182,10 +182,10 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_bp_kernel(
 
 static const int kBpCnDegrees[] = {3, 4, 5, 6, 7, 8, 9, 10, 19};
 
-int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row) {
+int build_onchip_bp_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   const int z = h->z;
   const int ncu = (h->n_cn + z - 1) / z, nbu = (h->n_vn + z - 1) / z;
-  h->bp_ok = 0;
+  h->bp.ok = 0;
   if (h->mb > 255 || h->nb > 255 || (z + 63) / 64 > 255) return SAMD_OK;
   std::vector<int32_t> row_off(h->mb, 0), col_ent((size_t)h->nb * kColStride, 0), col_deg(h->nb, 0);
 
@@ -203,20 +203,20 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
   }
   const size_t msg_bytes = (size_t)edges * z * 4;
   if (msg_bytes > 160 * 1024 || msg_bytes >= (1u << 18)) return SAMD_OK;   // the HBM-resident engine takes it
-  h->bp_edges = edges;
+  h->bp.edges = edges;
   size_t lds = msg_bytes + (size_t)nbu * z * 4;
-  h->bp_llr_global = 0;
-  if (lds > 160 * 1024) { h->bp_llr_global = 1; lds = msg_bytes; }
-  h->bp_waves = 16;
-  if (!h->bp_llr_global)
+  h->bp.llr_global = 0;
+  if (lds > 160 * 1024) { h->bp.llr_global = 1; lds = msg_bytes; }
+  h->bp.waves = 16;
+  if (!h->bp.llr_global)
     for (int nwc : {8, 4, 2, 1})
-      if (lds * (size_t)(kDecWaves / nwc) <= 160 * 1024) h->bp_waves = nwc;
+      if (lds * (size_t)(kDecWaves / nwc) <= 160 * 1024) h->bp.waves = nwc;
   if (opt_set("SAMD_ONCHIP_BP_WAVES")) {
     const std::string e_s = opt_str("SAMD_ONCHIP_BP_WAVES");
     const char* e = e_s.c_str();
     const int v = atoi(e);
-    if (!h->bp_llr_global && (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && lds * (size_t)(kDecWaves / v) <= 160 * 1024)
-      h->bp_waves = v;
+    if (!h->bp.llr_global && (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && lds * (size_t)(kDecWaves / v) <= 160 * 1024)
+      h->bp.waves = v;
   }
   // items: CN cost ~ degree (two phi evaluations per edge), VN cost ~ degree
   const int chunks = (z + 63) / 64;
@@ -228,8 +228,8 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
     for (int q = 0; q < chunks; ++q)
       if (c * z + q * 64 < h->n_vn) vi.push_back({col_deg[c] + 2, c | (q << 8)});
   std::vector<int32_t> cp, cl, vp, vl;
-  lpt_schedule(ci, h->bp_waves, &cp, &cl);
-  lpt_schedule(vi, h->bp_waves, &vp, &vl);
+  lpt_schedule(ci, h->bp.waves, &cp, &cl);
+  lpt_schedule(vi, h->bp.waves, &vp, &vl);
   {
     const std::vector<int> pc = item_priorities(ci, cp, cl), pv = item_priorities(vi, vp, vl);   // see ldpc5g.h
     for (size_t j = 0; j < cl.size(); ++j) cl[j] |= pc[j] << 24;
@@ -333,12 +333,12 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
   for (size_t i = 0; i < vpacked.size(); ++i) vi2.push_back({5 * vpacked_deg[i] + vn_ovh, (int32_t)i | (1 << 25)});
   std::vector<int32_t> mcp, mcl, mvp, mvl, mfp, mfl;
   // wave w runs on SIMD w % 4 as its (w / 4)-th oldest wave: optional capacities by age class (SAMD_MS_CAP="a,b,c,d")
-  std::vector<double> cap(h->bp_waves, 1.0);
+  std::vector<double> cap(h->bp.waves, 1.0);
   {
     double cls[4] = {1.0, 1.0, 1.0, 1.0};
     if (opt_set("SAMD_MS_CAP")) sscanf(opt_str("SAMD_MS_CAP").c_str(), "%lf,%lf,%lf,%lf", &cls[0], &cls[1], &cls[2], &cls[3]);
-    const int per_simd = std::max(1, h->bp_waves / 4);
-    for (int wv = 0; wv < h->bp_waves; ++wv) cap[wv] = cls[std::min(3, (wv / 4) * 4 / per_simd)];
+    const int per_simd = std::max(1, h->bp.waves / 4);
+    for (int wv = 0; wv < h->bp.waves; ++wv) cap[wv] = cls[std::min(3, (wv / 4) * 4 / per_simd)];
   }
   // Granularity: C2 has 29 variable-node items for 16 waves - the four single-chunk items of the degree-30 / 28 columns
   // are a wave's whole phase and leave it under-loaded, the other waves carry two pair items.  A pair item of the busiest
@@ -364,17 +364,17 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
       std::vector<size_t> order(its.size());
       std::iota(order.begin(), order.end(), 0);
       std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return its[a].first > its[b].first; });
-      std::vector<double> load(h->bp_waves, 0.0);
+      std::vector<double> load(h->bp.waves, 0.0);
       if (owner) owner->assign(its.size(), 0);
       for (size_t i : order) {
         int w = 0;
-        for (int q = 1; q < h->bp_waves; ++q)
+        for (int q = 1; q < h->bp.waves; ++q)
           if ((load[q] + its[i].first + 3) / cap[q] < (load[w] + its[i].first + 3) / cap[w]) w = q;
         load[w] += its[i].first + 3;
         if (owner) (*owner)[i] = w;
       }
       int mw = 0;
-      for (int q = 1; q < h->bp_waves; ++q) if (load[q] > load[mw]) mw = q;
+      for (int q = 1; q < h->bp.waves; ++q) if (load[q] > load[mw]) mw = q;
       return std::make_pair(load[mw], mw);
     };
     for (int t = 0; t < tries; ++t) {
@@ -405,10 +405,10 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
   refine(ci2, (int)opt_int("SAMD_MS_CN_REFINE", (chunks == 2 ? 4 : 0)),
          (int)opt_int("SAMD_MS_CN_REFINE_COST", 150),
          [&](int r) { const int d = (int)by_row[r].size(); return fused_col[r] >= 0 && d >= 5 && d <= 6; });
-  lpt_schedule(ci2, h->bp_waves, &mcp, &mcl, &cap);
-  lpt_schedule(vi2, h->bp_waves, &mvp, &mvl, &cap);
+  lpt_schedule(ci2, h->bp.waves, &mcp, &mcl, &cap);
+  lpt_schedule(vi2, h->bp.waves, &mvp, &mvl, &cap);
   const std::vector<int> cprio = item_priorities(ci2, mcp, mcl), vprio = item_priorities(vi2, mvp, mvl);
-  lpt_schedule(vf2, h->bp_waves, &mfp, &mfl);
+  lpt_schedule(vf2, h->bp.waves, &mfp, &mfl);
   for (int32_t o : mfp) mvp.push_back(o + (int32_t)mvl.size());
   mvl.insert(mvl.end(), mfl.begin(), mfl.end());
   std::vector<int32_t> tail_tab;
@@ -424,7 +424,7 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
       }
     }
   tail_tab.resize(tail_tab.size() + 2, 0);
-  h->ms_tail_sh = tail_sh;
+  h->ms.tail_sh = tail_sh;
   for (size_t j = 0; j < mcl.size(); ++j) {
     const int32_t d = mcl[j];
     if ((d >> 25) & 1) {                                      // packed tails: table base | key, last chunk | flag
@@ -460,38 +460,19 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
   cl2.resize(cl2.size() + 2, 0); vl2.resize(vl2.size() + 2, 0);
   // ---- grouped dispatch (ldpc5g_decode_msg_kernel): the items of every wave sorted by body type.  Only for codes whose
   // items are all full chunk pairs (Z a multiple of 128, no partially pruned base row) on 16 waves.
-  std::vector<int32_t> g_ptr, g_cn, g_vn, i_cn, i_vn, d_cn, d_vn;      // d_*: dataflow records, 4 ints per item (see below)
-  h->ms_g_ok = 0;
-  h->ms_df_ok = 0;
-  // dataflow readiness (ldpc5g_decode_msg_kernel, experiment of round 4): instead of two workgroup barriers per iteration,
-  // every item waits for the items it reads from and publishes its own completion through monotone counters in LDS -
-  // rowcnt[r] / colcnt[compact c] count the 64-lane chunks of row r / column c updated so far (`chunks` per iteration).
-  // A check-node item of row r in iteration `it` needs colcnt[c] >= chunks it for the non-fused columns c of its row, a
-  // variable-node item of column c needs rowcnt[r] >= chunks (it + 1) for the rows r of its column: the masks over at most
-  // 64 counters travel in the item's record {need lo, need hi, byte offset of the own counter, increment}.
-  std::vector<int> col_compact(h->nb, -1);
-  int n_compact = 0;
-  for (int c = 0; c < nbu; ++c)
-    if (!col_fused[c] && col_deg[c] > 0) col_compact[c] = n_compact++;
-  std::vector<unsigned long long> row_need(ncu, 0ull), col_need(h->nb, 0ull);
-  for (int r = 0; r < ncu; ++r)
-    for (auto& e : by_row[r]) {
-      const int c = e.first;
-      if (c < nbu && col_compact[c] >= 0 && col_compact[c] < 64) row_need[r] |= 1ull << col_compact[c];
-      if (c < nbu && r < 64) col_need[c] |= 1ull << r;
-    }
-  const bool df_shape = n_compact <= 64 && ncu <= 64;
-  if (z % 128 == 0 && h->n_cn % z == 0 && h->n_vn % z == 0 && h->bp_waves == 16 && groups < 2) {
+  std::vector<int32_t> g_ptr, g_cn, g_vn, i_cn, i_vn;
+  h->ms.g_ok = 0;
+  if (z % 128 == 0 && h->n_cn % z == 0 && h->n_vn % z == 0 && h->bp.waves == 16 && groups < 2) {
     bool ok = true;
     struct It { int cost, key; int32_t x, y; int idx, pr, q; };
     JitPlan* plan = new JitPlan();
-    plan->cn.resize(h->bp_waves); plan->vn.resize(h->bp_waves);
+    plan->cn.resize(h->bp.waves); plan->vn.resize(h->bp.waves);
     auto cost_in = [](const std::vector<std::pair<int, int32_t>>& items, int32_t id) {
       for (auto& it : items)
         if (it.second == id) return it.first;
       return 0;
     };
-    const int nwv = h->bp_waves;
+    const int nwv = h->bp.waves;
     for (int phase = 0; phase < 2 && ok; ++phase) {
       const std::vector<int32_t>& lp = phase ? mvp : mcp;
       const std::vector<int32_t>& ll = phase ? mvl : mcl;
@@ -536,7 +517,6 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
       if (!ok) break;
       std::vector<int32_t>& gl = phase ? g_vn : g_cn;
       std::vector<int32_t>& il = phase ? i_vn : i_cn;
-      std::vector<int32_t>& dl = phase ? d_vn : d_cn;
       for (int wv = 0; wv < nwv; ++wv) {
         g_ptr.push_back((int32_t)gl.size() / 2);
         // groups by type, the type with the most expensive items first; the group order is rotated by the wave's index
@@ -567,11 +547,6 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
             il.push_back(it.x | (prio << 24));
             il.push_back(it.y);
             (phase ? plan->vn : plan->cn)[wv].push_back(JitItem{it.idx, it.q, it.pr ? 2 : 1, prio});
-            const unsigned long long need = phase ? col_need[it.idx] : row_need[it.idx];
-            dl.push_back((int32_t)(unsigned)(need & 0xFFFFFFFFull));
-            dl.push_back((int32_t)(unsigned)(need >> 32));
-            dl.push_back(phase ? 8 * col_compact[it.idx] + 4 : 8 * it.idx);   // counters interleaved: {rowcnt[i], colcnt[i]} per lane
-            dl.push_back(it.pr ? 2 : 1);
           }
           gl.push_back(gq.front().key);
           gl.push_back((int32_t)(first | ((il.size() / 2) << 16)));
@@ -580,8 +555,8 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
       g_ptr.push_back((int32_t)gl.size() / 2);
       if (il.size() / 2 >= 65536) ok = false;
     }
-    h->ms_g_ok = ok && g_ptr.size() == (size_t)(2 * (nwv + 1)) ? 1 : 0;
-    if (h->ms_g_ok) {
+    h->ms.g_ok = ok && g_ptr.size() == (size_t)(2 * (nwv + 1)) ? 1 : 0;
+    if (h->ms.g_ok) {
       // the same schedule as data for the source generator of the specialised kernel (ldpc5g_jit.cpp)
       plan->z = z; plan->edges = edges; plan->ncu = ncu; plan->nbu = nbu;
       plan->row_off.resize(ncu); plan->row_deg.resize(ncu); plan->fused_col.assign(fused_col.begin(), fused_col.begin() + ncu);
@@ -596,53 +571,41 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
     }
     g_cn.resize(g_cn.size() + 2, 0); g_vn.resize(g_vn.size() + 2, 0);
     i_cn.resize(i_cn.size() + 4, 0); i_vn.resize(i_vn.size() + 4, 0);
-    d_cn.resize(d_cn.size() + 8, 0); d_vn.resize(d_vn.size() + 8, 0);
-    // every item of a row / column a full chunk pair's worth per iteration, the counters fit beside the messages
-    h->ms_df_ok = (h->ms_g_ok && df_shape && onchip_bp_lds_bytes(h) + 512 <= 160 * 1024) ? 1 : 0;
-    if (!h->ms_g_ok) g_ptr.assign(2 * (nwv + 1), 0);
+    if (!h->ms.g_ok) g_ptr.assign(2 * (nwv + 1), 0);
   }
-  int rc = upload(&h->bp_row_off, row_off.data(), row_off.size());
-  if (rc == SAMD_OK && h->ms_g_ok) rc = upload(&h->ms_g_ptr, g_ptr.data(), g_ptr.size());
-  if (rc == SAMD_OK && h->ms_g_ok) rc = upload(&h->ms_g_cn, g_cn.data(), g_cn.size());
-  if (rc == SAMD_OK && h->ms_g_ok) rc = upload(&h->ms_g_vn, g_vn.data(), g_vn.size());
-  if (rc == SAMD_OK && h->ms_g_ok) rc = upload(&h->ms_i_cn, i_cn.data(), i_cn.size());
-  if (rc == SAMD_OK && h->ms_g_ok) rc = upload(&h->ms_i_vn, i_vn.data(), i_vn.size());
-  if (rc == SAMD_OK && h->ms_df_ok) rc = upload(&h->ms_d_cn, d_cn.data(), d_cn.size());
-  if (rc == SAMD_OK && h->ms_df_ok) rc = upload(&h->ms_d_vn, d_vn.data(), d_vn.size());
-  if (rc == SAMD_OK) rc = upload(&h->bp_col_ent, col_ent.data(), col_ent.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_col_ent, col_ent2.data(), col_ent2.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_cn_ptr, mcp.data(), mcp.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_vn_ptr, mvp.data(), mvp.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_cn_list, cl2.data(), cl2.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_vn_list, vl2.data(), vl2.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_tail_tab, tail_tab.data(), tail_tab.size());
-  if (rc == SAMD_OK) rc = upload(&h->ms_vtail_tab, vtail_tab.data(), vtail_tab.size());
-  if (rc == SAMD_OK) rc = upload(&h->bp_col_deg, col_deg.data(), col_deg.size());
-  if (rc == SAMD_OK) rc = upload(&h->bp_cn_ptr, cp.data(), cp.size());
-  if (rc == SAMD_OK) rc = upload(&h->bp_cn_list, cl.data(), cl.size());
-  if (rc == SAMD_OK) rc = upload(&h->bp_vn_ptr, vp.data(), vp.size());
-  if (rc == SAMD_OK) rc = upload(&h->bp_vn_list, vl.data(), vl.size());
-  if (rc == SAMD_OK) h->bp_ok = 1;
+  int rc = h->bp.row_off.assign(row_off);
+  if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.g_ptr.assign(g_ptr);
+  if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.g_cn.assign(g_cn);
+  if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.g_vn.assign(g_vn);
+  if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.i_cn.assign(i_cn);
+  if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.i_vn.assign(i_vn);
+  if (rc == SAMD_OK) rc = h->bp.col_ent.assign(col_ent);
+  if (rc == SAMD_OK) rc = h->ms.col_ent.assign(col_ent2);
+  if (rc == SAMD_OK) rc = h->ms.cn_ptr.assign(mcp);
+  if (rc == SAMD_OK) rc = h->ms.vn_ptr.assign(mvp);
+  if (rc == SAMD_OK) rc = h->ms.cn_list.assign(cl2);
+  if (rc == SAMD_OK) rc = h->ms.vn_list.assign(vl2);
+  if (rc == SAMD_OK) rc = h->ms.tail_tab.assign(tail_tab);
+  if (rc == SAMD_OK) rc = h->ms.vtail_tab.assign(vtail_tab);
+  if (rc == SAMD_OK) rc = h->bp.col_deg.assign(col_deg);
+  if (rc == SAMD_OK) rc = h->bp.cn_ptr.assign(cp);
+  if (rc == SAMD_OK) rc = h->bp.cn_list.assign(cl);
+  if (rc == SAMD_OK) rc = h->bp.vn_ptr.assign(vp);
+  if (rc == SAMD_OK) rc = h->bp.vn_list.assign(vl);
+  if (rc == SAMD_OK) h->bp.ok = 1;
   return rc;
-}
-
-void free_onchip_bp_tables(samd_ldpc5g* h) {
-  (void)hipFree(h->bp_row_off); (void)hipFree(h->bp_col_ent); (void)hipFree(h->bp_col_deg); (void)hipFree(h->ms_col_ent); (void)hipFree(h->ms_cn_list); (void)hipFree(h->ms_cn_ptr); (void)hipFree(h->ms_vn_ptr); (void)hipFree(h->ms_vn_list); (void)hipFree(h->ms_tail_tab); (void)hipFree(h->ms_vtail_tab);
-  (void)hipFree(h->ms_g_ptr); (void)hipFree(h->ms_g_cn); (void)hipFree(h->ms_g_vn); (void)hipFree(h->ms_i_cn); (void)hipFree(h->ms_i_vn);
-  (void)hipFree(h->ms_d_cn); (void)hipFree(h->ms_d_vn);
-  (void)hipFree(h->bp_cn_ptr); (void)hipFree(h->bp_cn_list); (void)hipFree(h->bp_vn_ptr); (void)hipFree(h->bp_vn_list);
 }
 
 size_t onchip_bp_lds_bytes(const samd_ldpc5g* h) {
   const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)h->bp_edges * h->z * 4 + (h->bp_llr_global ? 0 : (size_t)nbu * h->z * 4);
+  return (size_t)h->bp.edges * h->z * 4 + (h->bp.llr_global ? 0 : (size_t)nbu * h->z * 4);
 }
 
 int onchip_bp_grid(const samd_ldpc5g* h, int batch) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t per_cu = std::min<size_t>((size_t)(kDecWaves / h->bp_waves), std::max<size_t>(1, (160 * 1024) / onchip_bp_lds_bytes(h)));
+  const size_t per_cu = std::min<size_t>((size_t)(kDecWaves / h->bp.waves), std::max<size_t>(1, (160 * 1024) / onchip_bp_lds_bytes(h)));
   size_t grid = std::min<size_t>((size_t)batch, (size_t)cus * per_cu);
   // SAMD_ONCHIP_GRID=<n>: fewer workgroups than the chip holds (test hook: every workgroup then decodes several
   // codewords in sequence, which exercises the grid-stride loop and the reuse of its workspace row on small batches)
@@ -651,7 +614,7 @@ int onchip_bp_grid(const samd_ldpc5g* h, int batch) {
 }
 
 size_t onchip_bp_workspace_bytes(const samd_ldpc5g* h, int batch) {
-  if (!h->bp_ok || !h->bp_llr_global || batch <= 0) return 0;
+  if (!h->bp.ok || !h->bp.llr_global || batch <= 0) return 0;
   const int nbu = (h->n_vn + h->z - 1) / h->z;
   return (size_t)onchip_bp_grid(h, batch) * nbu * h->z * sizeof(float) + 256;
 }
@@ -659,12 +622,12 @@ size_t onchip_bp_workspace_bytes(const samd_ldpc5g* h, int batch) {
 int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
                      float llr_max, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes,
                      hipStream_t st) {
-  if (!h->bp_ok) {
+  if (!h->bp.ok) {
     set_error("messages of this code do not fit in LDS");
     return SAMD_ERR_UNSUPPORTED;
   }
   float* llr_ws = nullptr;
-  if (h->bp_llr_global) {
+  if (h->bp.llr_global) {
     if (!workspace || workspace_bytes < onchip_bp_workspace_bytes(h, batch)) {
       set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
       return SAMD_ERR_WORKSPACE;
@@ -685,17 +648,17 @@ int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int bat
       SAMD_BP_K(SAMD_CN_BOXPLUS, 4, false),      SAMD_BP_K(SAMD_CN_BOXPLUS, 2, false),
       SAMD_BP_K(SAMD_CN_BOXPLUS, 1, false),      SAMD_BP_K(SAMD_CN_BOXPLUS, 16, true)};
 #undef SAMD_BP_K
-  const int nw = h->bp_waves;
-  const int wi = h->bp_llr_global ? 5 : (nw == 16 ? 0 : nw == 8 ? 1 : nw == 4 ? 2 : nw == 2 ? 3 : 4);
+  const int nw = h->bp.waves;
+  const int wi = h->bp.llr_global ? 5 : (nw == 16 ? 0 : nw == 8 ? 1 : nw == 4 ? 2 : nw == 2 ? 3 : 4);
   const int ki = (phi ? 0 : 12) + 2 * wi + (pow2 ? 1 : 0);
   // set on every launch: the attribute is per device and a process may drive several
   SAMD_SET_MAX_LDS(kerns[ki], 160 * 1024);
   const int nbu = (h->n_vn + h->z - 1) / h->z;
   const RateMatch rm = make_rate_match(h);
   hipLaunchKernelGGL(kerns[ki], dim3(onchip_bp_grid(h, batch)), dim3(nw * 64), onchip_bp_lds_bytes(h), st, llr, out, llr_ws, rm,
-                     h->n_cn, nbu, batch, num_iter, llr_max, hard_out, return_infobits, h->bp_edges * h->z,
-                     h->bp_row_off, h->bp_col_ent, h->bp_col_deg, h->bp_cn_ptr, h->bp_cn_list,
-                     h->bp_vn_ptr, h->bp_vn_list);
+                     h->n_cn, nbu, batch, num_iter, llr_max, hard_out, return_infobits, h->bp.edges * h->z,
+                     h->bp.row_off.get(), h->bp.col_ent.get(), h->bp.col_deg.get(), h->bp.cn_ptr.get(), h->bp.cn_list.get(),
+                     h->bp.vn_ptr.get(), h->bp.vn_list.get());
   return launch_status();
 }
 

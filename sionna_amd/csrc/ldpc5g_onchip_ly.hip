@@ -411,8 +411,8 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_ly_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ host tables
-int build_onchip_ly_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row) {
-  h->ly_ok = 0;
+int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
+  h->ly.ok = 0;
   const int z = h->z;
   const int ncu = (h->n_cn + z - 1) / z, nbu = (h->n_vn + z - 1) / z;
   // (lifting sizes below 16 stay on the HBM-resident engine, which runs many codewords side by side: Z = 11 is a tie,
@@ -827,51 +827,45 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pa
   }
   if (NW == 0) return SAMD_OK;
   const bool have_parts = abl == 0 && !opt_set("SAMD_LY_NOSPLIT") && build_lists(true, NW, parts) == 0 && parts.scratch_bytes > 0;
-  h->ly_waves = NW;
-  h->ly_lds_bytes = (int)lds;
-  h->ly_zero_off = zero_base / 4;
-  h->ly_msg_floats = edges * z;
-  h->ly_n_ext = n_ext;
-  h->ly_groups = (int)groups.size();
-  h->ly_bp_lds_bytes = have_parts ? (int)lds + parts.scratch_bytes : 0;
-  int rc = upload(&h->ly_rec_ptr, whole.rec_ptr.data(), whole.rec_ptr.size());
-  if (rc == SAMD_OK) rc = upload(&h->ly_recs, whole.recs.data(), whole.recs.size());
-  if (rc == SAMD_OK && have_parts) rc = upload(&h->ly_bp_rec_ptr, parts.rec_ptr.data(), parts.rec_ptr.size());
-  if (rc == SAMD_OK && have_parts) rc = upload(&h->ly_bp_recs, parts.recs.data(), parts.recs.size());
-  if (rc == SAMD_OK && have_parts) rc = upload(&h->ly_bp_slot_tab, parts.slot_tab.data(), parts.slot_tab.size());
-  if (rc == SAMD_OK) rc = upload(&h->ly_ent_tab, ent_tab.data(), ent_tab.size());
-  if (rc == SAMD_OK) rc = upload(&h->ly_xt_index, xt_index.data(), xt_index.size());
-  if (rc == SAMD_OK) rc = upload(&h->ly_slot_tab, whole.slot_tab.data(), whole.slot_tab.size());
-  if (rc == SAMD_OK) h->ly_ok = 1;
+  h->ly.waves = NW;
+  h->ly.lds_bytes = (int)lds;
+  h->ly.zero_off = zero_base / 4;
+  h->ly.msg_floats = edges * z;
+  h->ly.n_ext = n_ext;
+  h->ly.groups = (int)groups.size();
+  h->ly.bp_lds_bytes = have_parts ? (int)lds + parts.scratch_bytes : 0;
+  int rc = h->ly.rec_ptr.assign(whole.rec_ptr);
+  if (rc == SAMD_OK) rc = h->ly.recs.assign(whole.recs);
+  if (rc == SAMD_OK && have_parts) rc = h->ly.bp_rec_ptr.assign(parts.rec_ptr);
+  if (rc == SAMD_OK && have_parts) rc = h->ly.bp_recs.assign(parts.recs);
+  if (rc == SAMD_OK && have_parts) rc = h->ly.bp_slot_tab.assign(parts.slot_tab);
+  if (rc == SAMD_OK) rc = h->ly.ent_tab.assign(ent_tab);
+  if (rc == SAMD_OK) rc = h->ly.xt_index.assign(xt_index);
+  if (rc == SAMD_OK) rc = h->ly.slot_tab.assign(whole.slot_tab);
+  if (rc == SAMD_OK) h->ly.ok = 1;
   return rc;
-}
-
-void free_onchip_ly_tables(samd_ldpc5g* h) {
-  (void)hipFree(h->ly_rec_ptr); (void)hipFree(h->ly_recs); (void)hipFree(h->ly_ent_tab);
-  (void)hipFree(h->ly_xt_index); (void)hipFree(h->ly_slot_tab);
-  (void)hipFree(h->ly_bp_rec_ptr); (void)hipFree(h->ly_bp_recs); (void)hipFree(h->ly_bp_slot_tab);
 }
 
 static int ly_grid(const samd_ldpc5g* h, int batch) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  int grid = std::min(batch, cus * (16 / std::max(4, h->ly_waves)));
+  int grid = std::min(batch, cus * (16 / std::max(4, h->ly.waves)));
   if (h->opt.onchip_grid > 0) grid = std::min(grid, h->opt.onchip_grid);
   return grid;
 }
 
 size_t onchip_ly_workspace_bytes(const samd_ldpc5g* h, int batch) {
-  if (!h->ly_ok || batch <= 0) return 0;
+  if (!h->ly.ok || batch <= 0) return 0;
   const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)ly_grid(h, batch) * (size_t)(nbu + h->ly_n_ext) * h->z * sizeof(float) + 256;
+  return (size_t)ly_grid(h, batch) * (size_t)(nbu + h->ly.n_ext) * h->z * sizeof(float) + 256;
 }
 
 int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode, float llr_max,
                      float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes, hipStream_t st) {
   const bool minsum = cn_mode == SAMD_CN_MINSUM || cn_mode == SAMD_CN_OFFSET_MINSUM;
   const bool phi = cn_mode == SAMD_CN_BOXPLUS_PHI || cn_mode == SAMD_CN_BOXPLUS_PHI_FAST;
-  if (!h->ly_ok || !(minsum || phi)) {
+  if (!h->ly.ok || !(minsum || phi)) {
     set_error("layered on-chip engine: code or rule not covered (the HBM-resident scheduled engine takes it)");
     return SAMD_ERR_UNSUPPORTED;
   }
@@ -897,12 +891,13 @@ int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int bat
   const RateMatch rm = make_rate_match(h);
   const float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
   // the boxplus rules walk the lists with split check-node items where the code has them (more LDS: the parts' scratch)
-  const bool parts = !minsum && h->ly_bp_lds_bytes > 0;
-  hipLaunchKernelGGL(fn, dim3(ly_grid(h, batch)), dim3(64 * h->ly_waves), (size_t)(parts ? h->ly_bp_lds_bytes : h->ly_lds_bytes), st, llr, out, ws,
-                     rm, nbu, batch, num_iter, llr_max, off, hard_out, return_infobits, h->ly_msg_floats, h->ly_n_ext,
-                     h->ly_zero_off, 64 * h->ly_waves, parts ? h->ly_bp_rec_ptr : h->ly_rec_ptr,
-                     reinterpret_cast<const int4*>(parts ? h->ly_bp_recs : h->ly_recs), h->ly_ent_tab, h->ly_xt_index,
-                     parts ? h->ly_bp_slot_tab : h->ly_slot_tab);
+  const bool parts = !minsum && h->ly.bp_lds_bytes > 0;
+  const samd::Ldpc5gLayered& t = h->ly;
+  hipLaunchKernelGGL(fn, dim3(ly_grid(h, batch)), dim3(64 * t.waves), (size_t)(parts ? t.bp_lds_bytes : t.lds_bytes), st,
+                     llr, out, ws, rm, nbu, batch, num_iter, llr_max, off, hard_out, return_infobits, t.msg_floats, t.n_ext,
+                     t.zero_off, 64 * t.waves, parts ? t.bp_rec_ptr.get() : t.rec_ptr.get(),
+                     reinterpret_cast<const int4*>(parts ? t.bp_recs.get() : t.recs.get()), t.ent_tab.get(),
+                     t.xt_index.get(), parts ? t.bp_slot_tab.get() : t.slot_tab.get());
   return launch_status();
 }
 

@@ -560,67 +560,12 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
     int msg_floats, const int32_t* __restrict__ col_ent, const int32_t* __restrict__ vn_ptr,
     const int2* __restrict__ vn_list, const int32_t* __restrict__ g_ptr, const int2* __restrict__ g_cn,
     const int2* __restrict__ g_vn, const int2* __restrict__ i_cn, const int2* __restrict__ i_vn, int lds_bar, int phi_lds
-#ifdef SAMD_MS_DF
-    , const int4* __restrict__ d_cn, const int4* __restrict__ d_vn, int df_cnt_off, int df_chunks
-#endif
     ) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if ((unsigned)(size_t)(lds_f32*)smem != 0u) __builtin_trap();      // see lds_ld
   constexpr int NW = 16, NT = NW * 64;
   const unsigned phi_base = (MODE == SAMD_CN_BOXPLUS_PHI && phi_lds) ? 4u * (unsigned)(msg_floats + (LLRG ? 0 : nbu * p.z)) : kPhiNoLds;
   if (phi_base != kPhiNoLds) { phi_tab_stage(phi_base, (int)threadIdx.x); __syncthreads(); }
-#ifdef SAMD_MS_DF
-  // Dataflow readiness (df_cnt_off >= 0; round 4, SAMD_MS_DATAFLOW): no workgroup barrier inside the iteration loop.  64
-  // {rowcnt, colcnt} counter pairs sit at byte offset df_cnt_off of LDS; an item polls the pair array once (one 8-byte
-  // LDS read per lane, issued one item ahead), tests the counters its record names against the iteration's threshold
-  // and, after its last store, adds its chunk count to its own counter.  LDS serves a wave's operations in order, so the
-  // counter update is visible after the item's messages and a consumer's loads are issued after its successful poll.
-  const bool df = df_cnt_off >= 0;
-  const unsigned df_a = (unsigned)df_cnt_off + 8u * (unsigned)(threadIdx.x & 63);
-  typedef unsigned df_u32x2 __attribute__((ext_vector_type(2)));
-  typedef __attribute__((address_space(3))) volatile df_u32x2 lds_vu2;
-  typedef __attribute__((address_space(3))) unsigned lds_u32;
-  df_u32x2 df_pv = {0u, 0u};
-#define SAMD_DF_POLL() df_pv = *(lds_vu2*)(uintptr_t)df_a
-#define SAMD_DF_WAIT(FIELD, THR, NLO, NHI)                                                                      \
-  if (df) {                                                                                                      \
-    const unsigned long long need_ = ((unsigned long long)(unsigned)(NHI) << 32) | (unsigned)(NLO);             \
-    unsigned spins_ = 0;                                                                                         \
-    while ((__ballot(df_pv.FIELD >= (unsigned)(THR)) & need_) != need_ && spins_++ < (1u << 16)) {               \
-      __builtin_amdgcn_s_sleep(1);                                                                               \
-      SAMD_DF_POLL();                                                                                            \
-    }                                                                                                            \
-    asm volatile("" ::: "memory");                                                                               \
-    SAMD_DF_POLL();                                  /* for the wave's next item (re-polled there if stale) */   \
-  }
-#define SAMD_DF_DONE(OWN, INC)                                                                                   \
-  if (df) {                                                                                                      \
-    if ((threadIdx.x & 63) == 0)                                                                                 \
-      asm volatile("ds_add_u32 %0, %1" ::"v"((unsigned)df_cnt_off + (unsigned)(OWN)), "v"((unsigned)(INC)) : "memory"); \
-  }
-#define SAMD_DF_CN_FIRST int4 dnx = df ? d_cn[tb] : make_int4(0, 0, 0, 0);
-#define SAMD_DF_CN_REC                                                                                           \
-  const int dn0 = __builtin_amdgcn_readfirstlane(dnx.x), dn1 = __builtin_amdgcn_readfirstlane(dnx.y);            \
-  const int down = __builtin_amdgcn_readfirstlane(dnx.z), dinc = __builtin_amdgcn_readfirstlane(dnx.w);
-#define SAMD_DF_CN_NEXT if (df) dnx = d_cn[t + 1];
-#define SAMD_DF_VN_REC                                                                                           \
-  int vdn0 = 0, vdn1 = 0, vdown = 0, vdinc = 0;                                                                  \
-  if (df) {                                                                                                      \
-    const int4 dv = d_vn[t];                                                                                     \
-    vdn0 = __builtin_amdgcn_readfirstlane(dv.x); vdn1 = __builtin_amdgcn_readfirstlane(dv.y);                    \
-    vdown = __builtin_amdgcn_readfirstlane(dv.z); vdinc = __builtin_amdgcn_readfirstlane(dv.w);                  \
-  }
-#else
-  // (the dataflow-readiness experiment of round 4 lives behind -DSAMD_MS_DF, `make dataflow`: measured slower than the two
-  // barriers, profiles/r04_df_ab.txt; the product kernel carries none of it)
-  constexpr bool df = false;
-#define SAMD_DF_WAIT(FIELD, THR, NLO, NHI)
-#define SAMD_DF_DONE(OWN, INC)
-#define SAMD_DF_CN_FIRST
-#define SAMD_DF_CN_REC
-#define SAMD_DF_CN_NEXT
-#define SAMD_DF_VN_REC
-#endif
   constexpr bool POW2 = ZM >= 1;
   constexpr unsigned Z4C = ZM == 2 ? 512u : 0u;
   const unsigned z = ZM == 2 ? 128u : (unsigned)p.z, z4 = 4u * z;
@@ -645,9 +590,6 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
     const float* row = llr_in + (size_t)b * p.n;
     for (int v = tid; v < nx; v += NT)
       llr[v] = (v < n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
-#ifdef SAMD_MS_DF
-    if (df && tid < 128) *(lds_u32*)(uintptr_t)((unsigned)df_cnt_off + 4u * (unsigned)tid) = 0u;
-#endif
     __syncthreads();
     for (int seg = 0; seg < 2; ++seg) {                              // v2c of iteration 0 = channel LLR, all columns
       const int t0 = seg ? f0 : v0, t1 = seg ? f1 : v1;
@@ -687,17 +629,13 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
 #define SAMD_MSG_CN_(KEY, D, F, NCHC)                                                                             \
   case KEY: {                                                                                                     \
     int2 nxt = i_cn[tb];                                                                                          \
-    SAMD_DF_CN_FIRST                                                                                              \
     for (int t = tb; t < te; ++t) {                                                                               \
       const unsigned ix = (unsigned)__builtin_amdgcn_readfirstlane(nxt.x);                                        \
       const int iy = __builtin_amdgcn_readfirstlane(nxt.y);                                                       \
-      SAMD_DF_CN_REC                                                                                              \
-      if (t + 1 < te) { nxt = i_cn[t + 1]; SAMD_DF_CN_NEXT }                                                      \
+      if (t + 1 < te) nxt = i_cn[t + 1];                                                                          \
       const int pr = (int)(ix >> 24);                                                                             \
       if (pr != cur_prio) { onchip_setprio(pr); cur_prio = pr; }                                                  \
-      SAMD_DF_WAIT(y, df_chunks * it, dn0, dn1)                                                                   \
       ms_cn_row<D, NCHC, F, MODE, Z4C, VAR>((ix & 0xFFFFFFu) + lane4, z4, llr_max, offset, llr + iy + lane, last, phi_base); \
-      SAMD_DF_DONE(down, dinc)                                                                                    \
       SAMD_ITRACE(KEY)                                                                                            \
     }                                                                                                             \
   } break;
@@ -717,7 +655,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
 #undef SAMD_MSG_CN
 #undef SAMD_MSG_CN_
       }
-      if (!df) ms_phase_barrier(last || !lds_bar);
+      ms_phase_barrier(last || !lds_bar);
       SAMD_ITRACE(2000)
       // ---------------- VN phase: the channel LLRs of an item are fetched one item ahead (across group boundaries: the
       // items of a wave are consecutive in i_vn), its list entry two ahead - the entry then sits in scalar registers when
@@ -746,11 +684,8 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
       const int pr = (int)(ix >> 24);                                                                             \
       if (pr != cur_prio) { onchip_setprio(pr); cur_prio = pr; }                                                  \
       const unsigned zz4 = ((unsigned)iy >> 20) * 256u + lane4;                                                    \
-      SAMD_DF_VN_REC                                                                                              \
-      SAMD_DF_WAIT(x, df_chunks * (it + 1), vdn0, vdn1)                                                           \
       ms_vn_col<D, NCHV, POW2, false, (ZM == 2 && NCHV == 2)>(col_ent + (iy & 0xFFFFF), zz4, zwv,                 \
                                                               llr + (ix & 0x7FFFFFu) + lane, l0, l1, llr_max, last); \
-      SAMD_DF_DONE(vdown, vdinc)                                                                                  \
       SAMD_ITRACE(2000 + KEY)                                                                                     \
       cur = nxt; nxt = nxt2; l0 = n0; l1 = n1;                                                                    \
     }                                                                                                             \
@@ -771,7 +706,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
 #undef SAMD_MSG_VN
         }
       }
-      if (!df || last) ms_phase_barrier(last || !lds_bar);       // dataflow: only the output phase needs everybody
+      ms_phase_barrier(last || !lds_bar);
       SAMD_ITRACE(3000)
     }
     // ---------------- output (decoding.py:620-626, 1486-1531); llr[] now holds the marginals
@@ -792,14 +727,6 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
   }
 }
 
-#undef SAMD_DF_POLL
-#undef SAMD_DF_WAIT
-#undef SAMD_DF_DONE
-#undef SAMD_DF_CN_FIRST
-#undef SAMD_DF_CN_REC
-#undef SAMD_DF_CN_NEXT
-#undef SAMD_DF_VN_REC
-
 #if defined(SAMD_MS_TRACE) && defined(SAMD_MS_MAIN_TU)
 }  // namespace samd
 extern "C" int samd_debug_set_ms_trace(unsigned long long* p) {
@@ -812,12 +739,12 @@ template <int MODE>
 static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
                      float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
                      size_t workspace_bytes, hipStream_t st) {
-  if (!h->bp_ok || !h->ms_col_ent || !h->ms_cn_list || !h->ms_vn_list || !h->ms_vn_ptr) {
+  if (!h->bp.ok || !h->ms.col_ent.get() || !h->ms.cn_list.get() || !h->ms.vn_list.get() || !h->ms.vn_ptr.get()) {
     set_error("messages of this code do not fit in LDS");
     return SAMD_ERR_UNSUPPORTED;
   }
   float* llr_ws = nullptr;
-  if (h->bp_llr_global) {
+  if (h->bp.llr_global) {
     if (!workspace || workspace_bytes < onchip_bp_workspace_bytes(h, batch)) {
       set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
       return SAMD_ERR_WORKSPACE;
@@ -825,15 +752,11 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
     llr_ws = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
   }
   const bool pow2 = (h->z & (h->z - 1)) == 0;
-  if (h->ms_g_ok && h->bp_waves == 16 && !h->opt.ms_nogroup) {
+  if (h->ms.g_ok && h->bp.waves == 16 && !h->opt.ms_nogroup) {
     // grouped dispatch: the same items, sorted by body type per wave (see ldpc5g_decode_msg_kernel)
     typedef void (*gkern_t)(const float*, float*, float*, RateMatch, int, int, int, int, float, float, int, int, int,
                             const int32_t*, const int32_t*, const int2*, const int32_t*, const int2*, const int2*,
-                            const int2*, const int2*, int, int
-#ifdef SAMD_MS_DF
-                            , const int4*, const int4*, int, int
-#endif
-                            );
+                            const int2*, const int2*, int, int);
     constexpr int V1 = MODE == SAMD_CN_MINSUM ? 1 : 0;        // the bit-operation variant exists for min-sum only
 #define SAMD_MSG_K(V) {ldpc5g_decode_msg_kernel<0, false, MODE, V>, ldpc5g_decode_msg_kernel<1, false, MODE, V>, \
                        ldpc5g_decode_msg_kernel<2, false, MODE, V>, ldpc5g_decode_msg_kernel<0, true, MODE, V>,  \
@@ -842,33 +765,24 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
 #undef SAMD_MSG_K
     const int zm = (h->z == 128 && !h->opt.ms_noz128) ? 2 : (pow2 ? 1 : 0);
     const int var = h->opt.ms_var;                             // bit-operation variant: default
-    const gkern_t fn = gk[var][(h->bp_llr_global ? 3 : 0) + zm];
+    const gkern_t fn = gk[var][(h->bp.llr_global ? 3 : 0) + zm];
     SAMD_SET_MAX_LDS(fn, 160 * 1024);
     const int nbu_g = (h->n_vn + h->z - 1) / h->z;
     const RateMatch rm_g = make_rate_match(h);
     const float off_g = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
-#ifdef SAMD_MS_DF
-    const bool use_df = h->ms_df_ok && h->opt.ms_dataflow;       // development build + switch (SAMD_MS_DATAFLOW=1)
-#else
-    const bool use_df = false;
-#endif
     // boxplus-phi: 512 bytes behind the messages for the table of the defined logarithm when they fit (else global memory)
     const int phi_lds_g = MODE == SAMD_CN_BOXPLUS_PHI ? 1 : 0;
-    if (phi_lds_g && onchip_bp_lds_bytes(h) + 512 + (use_df ? 512 : 0) > 160 * 1024) {
+    if (phi_lds_g && onchip_bp_lds_bytes(h) + 512 > 160 * 1024) {
       set_error("no room for the boxplus-phi table beside the messages");
       return SAMD_ERR_UNSUPPORTED;                             // the caller runs the first boxplus kernel (table from global memory)
     }
-    hipLaunchKernelGGL(fn, dim3(onchip_bp_grid(h, batch)), dim3(1024), onchip_bp_lds_bytes(h) + (use_df ? 512 : 0) + (phi_lds_g ? 512 : 0), st, llr, out, llr_ws, rm_g,
-                       h->n_cn, nbu_g, batch, num_iter, llr_max, off_g, hard_out, return_infobits, h->bp_edges * h->z,
-                       h->ms_col_ent, h->ms_vn_ptr, reinterpret_cast<const int2*>(h->ms_vn_list), h->ms_g_ptr,
-                       reinterpret_cast<const int2*>(h->ms_g_cn), reinterpret_cast<const int2*>(h->ms_g_vn),
-                       reinterpret_cast<const int2*>(h->ms_i_cn), reinterpret_cast<const int2*>(h->ms_i_vn),
-                       h->opt.ms_ldsbar, phi_lds_g
-#ifdef SAMD_MS_DF
-                       , reinterpret_cast<const int4*>(h->ms_d_cn), reinterpret_cast<const int4*>(h->ms_d_vn),
-                       use_df ? (int)onchip_bp_lds_bytes(h) : -1, (h->z + 63) / 64
-#endif
-                       );
+    hipLaunchKernelGGL(fn, dim3(onchip_bp_grid(h, batch)), dim3(1024), onchip_bp_lds_bytes(h) + (phi_lds_g ? 512 : 0), st,
+                       llr, out, llr_ws, rm_g, h->n_cn, nbu_g, batch, num_iter, llr_max, off_g, hard_out, return_infobits,
+                       h->bp.edges * h->z, h->ms.col_ent.get(), h->ms.vn_ptr.get(),
+                       reinterpret_cast<const int2*>(h->ms.vn_list.get()), h->ms.g_ptr.get(),
+                       reinterpret_cast<const int2*>(h->ms.g_cn.get()), reinterpret_cast<const int2*>(h->ms.g_vn.get()),
+                       reinterpret_cast<const int2*>(h->ms.i_cn.get()), reinterpret_cast<const int2*>(h->ms.i_vn.get()),
+                       h->opt.ms_ldsbar, phi_lds_g);
     return launch_status();
   }
   typedef void (*kern_t)(const float*, float*, float*, RateMatch, int, int, int, int, float, float, int, int, int,
@@ -879,9 +793,9 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
   static const kern_t kerns2[2][12] = {SAMD_MS_TAB(false), SAMD_MS_TAB(true)};
 #undef SAMD_MS_TAB
 #undef SAMD_MS_K
-  const kern_t* kerns = kerns2[h->ms_tail_sh < 6 ? 1 : 0];     // packed-tail items in the lists
-  const int nw = h->bp_waves;
-  const int wi = h->bp_llr_global ? 5 : (nw == 16 ? 0 : nw == 8 ? 1 : nw == 4 ? 2 : nw == 2 ? 3 : 4);
+  const kern_t* kerns = kerns2[h->ms.tail_sh < 6 ? 1 : 0];     // packed-tail items in the lists
+  const int nw = h->bp.waves;
+  const int wi = h->bp.llr_global ? 5 : (nw == 16 ? 0 : nw == 8 ? 1 : nw == 4 ? 2 : nw == 2 ? 3 : 4);
   const int ki = 2 * wi + (pow2 ? 1 : 0);
   SAMD_SET_MAX_LDS(kerns[ki], 160 * 1024);
   const int nbu = (h->n_vn + h->z - 1) / h->z;
@@ -894,12 +808,13 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
     set_error("no room for the boxplus-phi table beside the messages");
     return SAMD_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(kerns[ki], dim3(onchip_bp_grid(h, batch)), dim3(nw * 64), onchip_bp_lds_bytes(h) + (phi_lds ? 512 : 0), st, llr, out,
-                     llr_ws, rm, h->n_cn, nbu, batch, num_iter, llr_max, off, hard_out, return_infobits,
-                     h->bp_edges * h->z, h->ms_col_ent, h->ms_cn_ptr, reinterpret_cast<const int2*>(h->ms_cn_list),
-                     h->ms_vn_ptr, reinterpret_cast<const int2*>(h->ms_vn_list),
-                     reinterpret_cast<const int2*>(h->ms_tail_tab), h->ms_tail_sh,
-                     reinterpret_cast<const int2*>(h->ms_vtail_tab), phi_lds);
+  hipLaunchKernelGGL(kerns[ki], dim3(onchip_bp_grid(h, batch)), dim3(nw * 64), onchip_bp_lds_bytes(h) + (phi_lds ? 512 : 0),
+                     st, llr, out, llr_ws, rm, h->n_cn, nbu, batch, num_iter, llr_max, off, hard_out, return_infobits,
+                     h->bp.edges * h->z, h->ms.col_ent.get(), h->ms.cn_ptr.get(),
+                     reinterpret_cast<const int2*>(h->ms.cn_list.get()),
+                     h->ms.vn_ptr.get(), reinterpret_cast<const int2*>(h->ms.vn_list.get()),
+                     reinterpret_cast<const int2*>(h->ms.tail_tab.get()), h->ms.tail_sh,
+                     reinterpret_cast<const int2*>(h->ms.vtail_tab.get()), phi_lds);
   return launch_status();
 }
 

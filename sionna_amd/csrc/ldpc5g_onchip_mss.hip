@@ -333,11 +333,11 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_mss_kernel(
 }
 
 // ---------------------------------------------------------------- host: tables, workspace, launch
-int build_onchip_mss_tables(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row) {
+int build_onchip_mss_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   const int z = h->z;
   const int ncu = (h->n_cn + z - 1) / z, nbu = (h->n_vn + z - 1) / z;
-  h->sp_ok = 0;
-  if (h->bp_ok) return SAMD_OK;                               // everything fits in LDS: ldpc5g_onchip_ms.hip
+  h->sp.ok = 0;
+  if (h->bp.ok) return SAMD_OK;                               // everything fits in LDS: ldpc5g_onchip_ms.hip
   if (h->mb > 255 || h->nb > 255 || (z + 63) / 64 > 7) return SAMD_OK;
   static const int kDeg[] = {3, 4, 5, 6, 7, 8, 9, 10, 19};
   // longest prefix of rows whose messages fit in LDS
@@ -424,21 +424,16 @@ int build_onchip_mss_tables(samd_ldpc5g* h, const std::vector<std::vector<std::p
   cl2.resize(cl2.size() + 2, 0); vl2.resize(vl2.size() + 2, 0);
   // measured (tools/sweep_ldpc.py): with up to about a quarter of the edges in L2 this engine beats the compressed
   // state engine (+16 % at 4 %, +9 % at 26 %, even at 28 %); beyond that the L2 round trips of the VN phase dominate
-  h->sp_spill_pct = (eg * 100 + el + eg - 1) / (el + eg);     // min-sum uses this engine up to 27 %, see ldpc5g.hip
-  h->sp_lds_bytes = el * z * 4;
-  h->sp_g_floats = eg * z;
-  int rc = upload(&h->sp_col_ent, col_ent.data(), col_ent.size());
-  if (rc == SAMD_OK) rc = upload(&h->sp_cn_ptr, cp.data(), cp.size());
-  if (rc == SAMD_OK) rc = upload(&h->sp_vn_ptr, vp.data(), vp.size());
-  if (rc == SAMD_OK) rc = upload(&h->sp_cn_list, cl2.data(), cl2.size());
-  if (rc == SAMD_OK) rc = upload(&h->sp_vn_list, vl2.data(), vl2.size());
-  if (rc == SAMD_OK) h->sp_ok = 1;
+  h->sp.spill_pct = (eg * 100 + el + eg - 1) / (el + eg);     // min-sum uses this engine up to 27 %, see ldpc5g.hip
+  h->sp.lds_bytes = el * z * 4;
+  h->sp.g_floats = eg * z;
+  int rc = h->sp.col_ent.assign(col_ent);
+  if (rc == SAMD_OK) rc = h->sp.cn_ptr.assign(cp);
+  if (rc == SAMD_OK) rc = h->sp.vn_ptr.assign(vp);
+  if (rc == SAMD_OK) rc = h->sp.cn_list.assign(cl2);
+  if (rc == SAMD_OK) rc = h->sp.vn_list.assign(vl2);
+  if (rc == SAMD_OK) h->sp.ok = 1;
   return rc;
-}
-
-void free_onchip_mss_tables(samd_ldpc5g* h) {
-  (void)hipFree(h->sp_col_ent); (void)hipFree(h->sp_cn_ptr); (void)hipFree(h->sp_vn_ptr);
-  (void)hipFree(h->sp_cn_list); (void)hipFree(h->sp_vn_list);
 }
 
 static int mss_grid(const samd_ldpc5g* h, int batch) {
@@ -449,15 +444,15 @@ static int mss_grid(const samd_ldpc5g* h, int batch) {
 }
 
 size_t onchip_mss_workspace_bytes(const samd_ldpc5g* h, int batch) {
-  if (!h->sp_ok || batch <= 0) return 0;
+  if (!h->sp.ok || batch <= 0) return 0;
   const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)mss_grid(h, batch) * ((size_t)nbu * h->z + h->sp_g_floats) * sizeof(float) + 256;
+  return (size_t)mss_grid(h, batch) * ((size_t)nbu * h->z + h->sp.g_floats) * sizeof(float) + 256;
 }
 
 int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
                       float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
-  if (!h->sp_ok) {
+  if (!h->sp.ok) {
     set_error("no spill schedule for this code");
     return SAMD_ERR_UNSUPPORTED;
   }
@@ -479,10 +474,10 @@ int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int ba
   const int nbu = (h->n_vn + h->z - 1) / h->z;
   const RateMatch rm = make_rate_match(h);
   const float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
-  hipLaunchKernelGGL(fn, dim3(mss_grid(h, batch)), dim3(1024), h->sp_lds_bytes, st, llr, out, ws, rm, h->n_cn, nbu, batch,
-                     num_iter, llr_max, off, hard_out, return_infobits, h->sp_g_floats, h->sp_col_ent, h->sp_cn_ptr,
-                     reinterpret_cast<const int2*>(h->sp_cn_list), h->sp_vn_ptr,
-                     reinterpret_cast<const int2*>(h->sp_vn_list));
+  hipLaunchKernelGGL(fn, dim3(mss_grid(h, batch)), dim3(1024), h->sp.lds_bytes, st, llr, out, ws, rm, h->n_cn, nbu, batch,
+                     num_iter, llr_max, off, hard_out, return_infobits, h->sp.g_floats, h->sp.col_ent.get(),
+                     h->sp.cn_ptr.get(), reinterpret_cast<const int2*>(h->sp.cn_list.get()), h->sp.vn_ptr.get(),
+                     reinterpret_cast<const int2*>(h->sp.vn_list.get()));
   return launch_status();
 }
 

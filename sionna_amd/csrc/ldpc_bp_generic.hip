@@ -335,7 +335,7 @@ static void launch_vn_total(const samd_ldpc_graph* g, const float* msg, const fl
   const int bs4 = bs / 4;
   const dim3 grid((bs4 + kWave - 1) / kWave, (n_nodes + 3) / 4);
 #define SAMD_VT_LAUNCH(MAXD)                                                                          \
-  hipLaunchKernelGGL((vn_total_kernel<MAXD>), grid, blk, 0, st, msg, llr_t, xtot, g->vn_ptr, node_list, \
+  hipLaunchKernelGGL((vn_total_kernel<MAXD>), grid, blk, 0, st, msg, llr_t, xtot, g->vn_ptr.get(), node_list, \
                      n_nodes, bs4, (size_t)bs)
   if (g->max_dv <= 8) SAMD_VT_LAUNCH(8);
   else if (g->max_dv <= 32) SAMD_VT_LAUNCH(32);
@@ -350,16 +350,16 @@ static void launch_cn(const samd_ldpc_graph* g, float* msg, const float* aux, co
   const int bs4 = bs / 4;
   const dim3 grid((bs4 + kWave - 1) / kWave, (n_nodes + 3) / 4);
 #define SAMD_CN_LAUNCH(MAXD)                                                                    \
-  hipLaunchKernelGGL((cn_pass_kernel<MODE, MAXD, SRC>), grid, blk, 0, st, msg, aux, g->cn_ptr,   \
-                     g->cn_edge, g->cn_vn, node_list, n_nodes, bs4, (size_t)bs, llr_max, offset)
+  hipLaunchKernelGGL((cn_pass_kernel<MODE, MAXD, SRC>), grid, blk, 0, st, msg, aux, g->cn_ptr.get(),   \
+                     g->cn_edge.get(), g->cn_vn.get(), node_list, n_nodes, bs4, (size_t)bs, llr_max, offset)
   if (g->max_dc <= 8) SAMD_CN_LAUNCH(8);
   else if (g->max_dc <= 12) SAMD_CN_LAUNCH(12);
   else if (g->max_dc <= 20) SAMD_CN_LAUNCH(20);
   else if (g->max_dc <= 32) SAMD_CN_LAUNCH(32);
   else {
     const dim3 grid1((bs + kWave - 1) / kWave, (n_nodes + 3) / 4);
-    hipLaunchKernelGGL((cn_pass_bigdeg_kernel<MODE, SRC>), grid1, blk, 0, st, msg, aux, g->cn_ptr, g->cn_edge,
-                       g->cn_vn, node_list, n_nodes, bs, (size_t)bs, llr_max, offset);
+    hipLaunchKernelGGL((cn_pass_bigdeg_kernel<MODE, SRC>), grid1, blk, 0, st, msg, aux, g->cn_ptr.get(), g->cn_edge.get(),
+                       g->cn_vn.get(), node_list, n_nodes, bs, (size_t)bs, llr_max, offset);
   }
 #undef SAMD_CN_LAUNCH
 }
@@ -387,14 +387,14 @@ static void launch_vn(const samd_ldpc_graph* g, float* msg, const float* llr_t, 
   const int bs4 = bs / 4;
   const dim3 grid((bs4 + kWave - 1) / kWave, (g->num_vn + 3) / 4);
 #define SAMD_VN_LAUNCH(MAXD)                                                                          \
-  hipLaunchKernelGGL((vn_pass_kernel<MAXD, LAST>), grid, blk, 0, st, msg, llr_t, xhat_t, g->vn_ptr, \
+  hipLaunchKernelGGL((vn_pass_kernel<MAXD, LAST>), grid, blk, 0, st, msg, llr_t, xhat_t, g->vn_ptr.get(), \
                      g->num_vn, out_rows, bs4, (size_t)bs, llr_max)
   if (g->max_dv <= 8) SAMD_VN_LAUNCH(8);
   else if (g->max_dv <= 16) SAMD_VN_LAUNCH(16);
   else if (g->max_dv <= 32) SAMD_VN_LAUNCH(32);
   else {
     const dim3 grid1((bs + kWave - 1) / kWave, (g->num_vn + 3) / 4);
-    hipLaunchKernelGGL((vn_pass_bigdeg_kernel<LAST>), grid1, blk, 0, st, msg, llr_t, xhat_t, g->vn_ptr,
+    hipLaunchKernelGGL((vn_pass_bigdeg_kernel<LAST>), grid1, blk, 0, st, msg, llr_t, xhat_t, g->vn_ptr.get(),
                        g->num_vn, out_rows, bs, (size_t)bs, llr_max);
   }
 #undef SAMD_VN_LAUNCH
@@ -432,20 +432,16 @@ extern "C" int samd_ldpc_graph_create(const int32_t* cn_idx, const int32_t* vn_i
   g->num_edges = num_edges; g->num_cn = num_cn; g->num_vn = num_vn;
   g->max_dc = max_dc; g->max_dv = max_dv;
   g->h_cn_ptr = cn_ptr; g->h_cn_vn = cn_vn;
-  int rc = upload(&g->cn_ptr, cn_ptr.data(), cn_ptr.size());
-  if (rc == SAMD_OK) rc = upload(&g->cn_edge, cn_edge.data(), cn_edge.size());
-  if (rc == SAMD_OK) rc = upload(&g->cn_vn, cn_vn.data(), cn_vn.size());
-  if (rc == SAMD_OK) rc = upload(&g->vn_ptr, vn_ptr.data(), vn_ptr.size());
+  int rc = g->cn_ptr.assign(cn_ptr);
+  if (rc == SAMD_OK) rc = g->cn_edge.assign(cn_edge);
+  if (rc == SAMD_OK) rc = g->cn_vn.assign(cn_vn);
+  if (rc == SAMD_OK) rc = g->vn_ptr.assign(vn_ptr);
   if (rc != SAMD_OK) { samd_ldpc_graph_destroy(g); return rc; }
   *out = g;
   return SAMD_OK;
 }
 
-extern "C" void samd_ldpc_graph_destroy(samd_ldpc_graph_t* g) {
-  if (!g) return;
-  (void)hipFree(g->cn_ptr); (void)hipFree(g->cn_edge); (void)hipFree(g->cn_vn); (void)hipFree(g->vn_ptr);
-  delete g;
-}
+extern "C" void samd_ldpc_graph_destroy(samd_ldpc_graph_t* g) { delete g; }
 
 static inline size_t padded_batch(int batch) { return align_up((size_t)batch, 64); }
 
@@ -489,7 +485,7 @@ extern "C" int samd_ldpc_bp_decode_f32(const samd_ldpc_graph_t* g, const float* 
     xsrc = llr_t;  // decoding.py:603-608: x_hat = clipped input
     if (state_out && !state_in) {
       const dim3 grid((bs + 255) / 256, rows_grid(g->num_vn));
-      hipLaunchKernelGGL(init_v2c_kernel, grid, dim3(256), 0, st, msg, llr_t, g->vn_ptr, g->num_vn, (int)bs, bs);
+      hipLaunchKernelGGL(init_v2c_kernel, grid, dim3(256), 0, st, msg, llr_t, g->vn_ptr.get(), g->num_vn, (int)bs, bs);
     }
   }
   for (int it = 0; it < num_iter; ++it) {
@@ -536,19 +532,15 @@ extern "C" int samd_ldpc_schedule_create(const samd_ldpc_graph_t* g, const int32
   }
   auto* s = new samd_ldpc_schedule();
   s->num_sub = num_sub; s->width = width; s->num_cn = g->num_cn; s->vn_off = vn_off;
-  int rc = upload(&s->cn_list, cn_schedule, (size_t)num_sub * width);
-  if (rc == SAMD_OK) rc = upload(&s->vn_list, vn_list.data(), vn_list.size());
-  if (rc == SAMD_OK) rc = upload(&s->first_mask, mask.data(), mask.size());
+  int rc = s->cn_list.assign(cn_schedule, (size_t)num_sub * width);
+  if (rc == SAMD_OK) rc = s->vn_list.assign(vn_list);
+  if (rc == SAMD_OK) rc = s->first_mask.assign(mask);
   if (rc != SAMD_OK) { samd_ldpc_schedule_destroy(s); return rc; }
   *out = s;
   return SAMD_OK;
 }
 
-extern "C" void samd_ldpc_schedule_destroy(samd_ldpc_schedule_t* s) {
-  if (!s) return;
-  (void)hipFree(s->cn_list); (void)hipFree(s->vn_list); (void)hipFree(s->first_mask);
-  delete s;
-}
+extern "C" void samd_ldpc_schedule_destroy(samd_ldpc_schedule_t* s) { delete s; }
 
 extern "C" int samd_ldpc_bp_decode_scheduled_f32(const samd_ldpc_graph_t* g, const samd_ldpc_schedule_t* sched,
                                                  const float* llr_in, float* out, int out_cols, float* state,
@@ -585,19 +577,19 @@ extern "C" int samd_ldpc_bp_decode_scheduled_f32(const samd_ldpc_graph_t* g, con
   bool v2c_from_state = state_in != 0;  // only the very first sub-iteration sees the given v2c
   for (int it = 0; it < num_iter; ++it)
     for (int j = 0; j < sched->num_sub; ++j) {
-      const int32_t* cns = sched->cn_list + (size_t)j * sched->width;
+      const int32_t* cns = sched->cn_list.get() + (size_t)j * sched->width;
       int rc;
       if (v2c_from_state) {
         rc = launch_cn_mode<SRC_V2C>(g, cn_mode, msg, xtot, (int)bs, llr_max, offset, st, cns, sched->width);
         const dim3 grid(((int)bs + 255) / 256, rows_grid(g->num_cn));
-        hipLaunchKernelGGL(zero_inactive_kernel, grid, dim3(256), 0, st, msg, g->cn_ptr, g->cn_edge, sched->first_mask,
-                           g->num_cn, (int)bs, bs);
+        hipLaunchKernelGGL(zero_inactive_kernel, grid, dim3(256), 0, st, msg, g->cn_ptr.get(), g->cn_edge.get(),
+                           sched->first_mask.get(), g->num_cn, (int)bs, bs);
         v2c_from_state = false;
       } else {
         rc = launch_cn_mode<SRC_DERIVED>(g, cn_mode, msg, xtot, (int)bs, llr_max, offset, st, cns, sched->width);
       }
       if (rc != SAMD_OK) return rc;
-      launch_vn_total(g, msg, llr_t, xtot, sched->vn_list + sched->vn_off[j], sched->vn_off[j + 1] - sched->vn_off[j],
+      launch_vn_total(g, msg, llr_t, xtot, sched->vn_list.get() + sched->vn_off[j], sched->vn_off[j + 1] - sched->vn_off[j],
                       (int)bs, st);
     }
   {
@@ -609,7 +601,8 @@ extern "C" int samd_ldpc_bp_decode_scheduled_f32(const samd_ldpc_graph_t* g, con
       // nothing ran: the state is returned as given
     } else {
       const dim3 grid((batch + 255) / 256, rows_grid(g->num_vn));
-      hipLaunchKernelGGL(v2c_state_kernel, grid, dim3(256), 0, st, msg, xtot, g->vn_ptr, state, g->num_vn, batch, bs, llr_max);
+      hipLaunchKernelGGL(v2c_state_kernel, grid, dim3(256), 0, st, msg, xtot, g->vn_ptr.get(), state, g->num_vn, batch, bs,
+                         llr_max);
     }
   }
   return launch_status();
