@@ -210,6 +210,7 @@ __device__ __forceinline__ float sincf(float x) {
 // One workgroup per (b, rx, tx): g[p][l] = sinc(l - tau_p W) in LDS, then
 // h[ra, ta, t, l] = sum_p a[ra, ta, p, t] g[p][l]; optional in-block normalisation
 // (utils.py:337-347: c = mean over (ra, ta, t) of sum_l |h|^2).
+constexpr size_t kCirToTimeStaticLds = 256 * sizeof(float);   // red[] below
 __global__ void __launch_bounds__(256) cir_to_time_kernel(const float2* __restrict__ a, const float* __restrict__ tau,
                                                           float bandwidth, int l_min, int L, int num_rx, int RA,
                                                           int num_tx, int TA, int P, int T, int normalize,
@@ -420,11 +421,16 @@ extern "C" int samd_ofdm_demodulate_c128(const double* y, int rows, int in_len, 
 extern "C" int samd_cir_to_time_c64(float bandwidth, const float* a, const float* tau, int l_min, int l_max,
                                     int batch, int num_rx, int num_rx_ant, int num_tx, int num_tx_ant, int num_paths,
                                     int num_time_steps, int normalize, float* h_time, float* norm_scale, void* stream) {
-  SAMD_REQUIRE(a && tau && h_time && batch > 0 && l_max >= l_min && num_paths > 0 && num_time_steps > 0,
+  SAMD_REQUIRE(a && tau && h_time && batch >= 0 && l_max >= l_min && num_paths > 0 && num_time_steps > 0,
                "bad argument");
+  if (batch == 0) return SAMD_OK;
   const int L = l_max - l_min + 1;
   const size_t lds = (size_t)((num_paths * L + 1) & ~1) * sizeof(float) + (size_t)4 * 64 * L * sizeof(float2);   // sinc table + per-wave stage
-  SAMD_REQUIRE(lds <= 64 * 1024, "num_paths * l_tot too large for the LDS sinc table");
+  // a workgroup's LDS is the dynamic part plus the kernel's static red[256] (kCirToTimeStaticLds: 1024 bytes in the compiler's
+  // resource report for gfx950); a workgroup may hold 160 KiB, of which the runtime grants 64 KiB unless asked for more -
+  // and what can be asked for is the dynamic part: 160 KiB less the static bytes
+  SAMD_REQUIRE(lds + kCirToTimeStaticLds <= 160 * 1024, "num_paths * l_tot too large for the LDS sinc table");
+  if (lds + kCirToTimeStaticLds > 64 * 1024) SAMD_SET_MAX_LDS(cir_to_time_kernel, (int)(160 * 1024 - kCirToTimeStaticLds));
   cir_to_time_kernel<<<batch * num_rx * num_tx, 256, lds, (hipStream_t)stream>>>(
       (const float2*)a, tau, bandwidth, l_min, L, num_rx, num_rx_ant, num_tx, num_tx_ant, num_paths, num_time_steps,
       normalize, (float2*)h_time, normalize ? norm_scale : nullptr);
@@ -434,7 +440,8 @@ extern "C" int samd_cir_to_time_c64(float bandwidth, const float* a, const float
 extern "C" int samd_apply_time_channel_c64(const float* x, const float* h_time, const float* link_scale, int batch, int num_rx, int num_rx_ant,
                                            int num_tx, int num_tx_ant, int num_time_samples, int l_tot, float* y,
                                            void* stream) {
-  SAMD_REQUIRE(x && h_time && y && batch > 0 && num_time_samples > 0 && l_tot > 0, "bad argument");
+  SAMD_REQUIRE(x && h_time && y && batch >= 0 && num_time_samples > 0 && l_tot > 0, "bad argument");
+  if (batch == 0) return SAMD_OK;
   const int Tout = num_time_samples + l_tot - 1;
   const int ntb = (Tout + 255) / 256;
   SAMD_REQUIRE((long long)ntb * num_rx * num_rx_ant * batch < (1ll << 31), "grid too large");

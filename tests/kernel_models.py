@@ -412,3 +412,167 @@ def c2o_model_f32(freqs, a, tau, normalize, d, chain=None, mutation=None, spacin
     inv = inv[:, :, None, :, None, None, None]
     h.real, h.imag = hx * inv, hy * inv
     return h
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# cir_to_time_channel / ApplyTimeChannel (csrc/ofdm_time.hip): float32 restatements of cir_to_time_kernel and
+# apply_time_kernel in their summation order, the LDS stages as their index arithmetic on a flat array.  Held to
+# tests/time_channel_f32.py in tests/test_time_channel_host.py.  The library is built without contraction: a product and a
+# sum are one rounding each, which is what NumPy's float32 operations do.
+# ---------------------------------------------------------------------------------------------------------------------
+C2T_TILE = 9
+C2T_MUTATIONS = ("tail_tile_prev_weight", "stage_stride_minus", "stage_stride_plus", "cnt_short_row", "tau_next_tx", "table_unpadded",
+                 "mean_over_l")
+
+
+def c2t_lds_bytes(P, L):
+    """LDS of a cir_to_time_kernel workgroup as samd_cir_to_time_c64 counts it: the sinc table padded to an even count, four wave
+    stages of [64][L] float2, and the kernel's static red[256]"""
+    return ((P * L + 1) & ~1) * 4 + 4 * 64 * L * 8 + 256 * 4
+
+
+def c2t_model_f32(bandwidth, a, tau, l_min, l_max, normalize, defer=False, mutation=None):
+    """cir_to_time_kernel: one workgroup per (b, rx, tx); the sinc table g[p][l] at the start of the LDS, the per-wave stage
+    [64][L] of float2 behind it at the float offset (P L + 1) & ~1; per link and per pass of 64 time steps a wave computes lags in
+    tiles of 9 (p ascending), writes them to the stage at lane * L + l and copies min(64, T - t0) * L contiguous values out; a
+    thread's energy chain runs over everything it computed, the 256 chains meet in a tree.  -> h complex64, or (h unnormalised,
+    scale [b, rx, tx]) with ``defer``.  ``mutation``: one of C2T_MUTATIONS - a seeded fault that the bound has to catch.
+    "table_unpadded" puts the stage at P L; an 8-byte LDS access ignores the low three address bits, so for odd P L stage[0]
+    lands on the last weight of the table."""
+    f32 = np.float32
+    a, tau = np.asarray(a, np.complex64), np.asarray(tau, f32)
+    b_n, rx_n, ra_n, tx_n, ta_n, p_n, t_n = a.shape
+    L = l_max - l_min + 1
+    grp = b_n * rx_n * tx_n
+    nlk = ra_n * ta_n
+    ag = np.ascontiguousarray(a.transpose(0, 1, 3, 2, 4, 5, 6)).reshape(grp, nlk, p_n, t_n)
+    ax, ay = np.ascontiguousarray(ag.real), np.ascontiguousarray(ag.imag)
+    if mutation == "tau_next_tx":
+        tau = np.roll(tau, -1, axis=2)
+    tg = tau.reshape(grp, p_n)
+    # the table
+    lag = (l_min + np.arange(L)).astype(f32)
+    x = (lag[None, None, :] - (tg * f32(bandwidth))[:, :, None]).astype(f32)     # [grp, P, L]
+    y = (f32(3.14159265358979323846) * x).astype(f32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(x == 0, f32(1), np.sin(y.astype(np.float64)).astype(f32) / np.where(x == 0, f32(1), y)).astype(f32)
+    stride = L + {"stage_stride_minus": -1, "stage_stride_plus": 1}.get(mutation, 0)
+    base = p_n * L if mutation == "table_unpadded" else (p_n * L + 1) & ~1
+    base &= ~1                                                                   # float2 accesses are 8-byte aligned
+    lds = np.zeros((grp, base + 2 * (4 * 64 * L + 64 * (abs(stride - L) + 1))), f32)
+    lds[:, :p_n * L] = g.reshape(grp, p_n * L)
+    hx = np.zeros((grp, nlk, t_n * L), f32)
+    hy = np.zeros((grp, nlk, t_n * L), f32)
+    energy = np.zeros((grp, 256), f32)
+    lane = np.arange(64)
+    for lk in range(nlk):
+        for tb in range(0, t_n, 256):
+            for wv in range(4):
+                t0 = tb + 64 * wv
+                if t0 >= t_n:
+                    continue
+                t = t0 + lane
+                live = t < t_n
+                tc = np.minimum(t, t_n - 1)
+                sb = base + 2 * wv * 64 * L
+                for l0 in range(0, L, C2T_TILE):
+                    nj = min(C2T_TILE, L - l0)
+                    j = np.arange(nj)
+                    src = l0 - C2T_TILE if (mutation == "tail_tile_prev_weight" and nj < C2T_TILE and l0 > 0) else l0
+                    re = np.zeros((grp, 64, nj), f32)
+                    im = np.zeros((grp, 64, nj), f32)
+                    for p in range(p_n):
+                        w = lds[:, p * L + src:p * L + src + nj][:, None, :]     # read from the LDS: a clobbered weight shows
+                        vx = np.where(live, ax[:, lk, p, tc], f32(0))[:, :, None]
+                        vy = np.where(live, ay[:, lk, p, tc], f32(0))[:, :, None]
+                        re = re + vx * w
+                        im = im + vy * w
+                    assert re.dtype == f32
+                    off = sb + 2 * (lane[:, None] * stride + l0 + j[None, :])    # [64, nj] float offsets of the float2
+                    lds[:, off] = re
+                    lds[:, off + 1] = im
+                    for k in range(nj):                                          # zero for t >= T
+                        energy[:, 64 * wv:64 * wv + 64] += re[:, :, k] * re[:, :, k] + im[:, :, k] * im[:, :, k]
+                rows = min(64, t_n - t0)
+                if mutation == "cnt_short_row" and rows < 64:
+                    rows -= 1
+                cnt = rows * L
+                i = np.arange(cnt)
+                hx[:, lk, t0 * L + i] = lds[:, sb + 2 * i]
+                hy[:, lk, t0 * L + i] = lds[:, sb + 2 * i + 1]
+
+    def out(vx, vy):
+        h = np.empty((grp, nlk, t_n * L), np.complex64)
+        h.real, h.imag = vx, vy
+        h = h.reshape(b_n, rx_n, tx_n, ra_n, ta_n, t_n, L).transpose(0, 1, 3, 2, 4, 5, 6)
+        return np.ascontiguousarray(h)
+    if not normalize:
+        return (out(hx, hy), None) if defer else out(hx, hy)
+    red = energy.copy()
+    s = 128
+    while s > 0:
+        red[:, :s] = red[:, :s] + red[:, s:2 * s]
+        s >>= 1
+    n = nlk * t_n * (L if mutation == "mean_over_l" else 1)
+    c = np.sqrt((red[:, 0] / f32(n)).astype(f32)).astype(f32)
+    inv = np.where(c > 0, f32(1) / np.where(c > 0, c, f32(1)), f32(0)).astype(f32)
+    if defer:
+        return out(hx, hy), inv.reshape(b_n, rx_n, tx_n)
+    return out(hx * inv[:, None, None], hy * inv[:, None, None])
+
+
+APT_MUTATIONS = ("hi_short", "lo_late", "lo_early", "x_shift", "scale_other_tx")
+
+
+def apt_model_f32(x, h, link_scale=None, mutation=None):
+    """apply_time_kernel: one lane per output time step, 256 per block; per link (tx outer, ta inner) the block's 256 x L taps are
+    one contiguous piece of h, staged at hs[i] and read back at hs[lane * L + l]; l ascending from lo = max(0, t - (Tn - 1)) to
+    hi = min(t, L - 1); one accumulator pair over all links.  x is read through its flat storage, as the kernel's pointer
+    arithmetic does.  ``mutation``: one of APT_MUTATIONS."""
+    f32 = np.float32
+    x, h = np.asarray(x, np.complex64), np.asarray(h, np.complex64)
+    b_n, rx_n, ra_n, tx_n, ta_n, tout, L = h.shape
+    tn = tout - L + 1
+    xf = np.concatenate([x.reshape(-1), np.zeros(2, np.complex64)])              # the flat storage, two zeros behind it
+    xfx, xfy = np.ascontiguousarray(xf.real), np.ascontiguousarray(xf.imag)
+    hf = h.reshape(b_n, rx_n, ra_n, tx_n, ta_n, tout * L)
+    yx = np.zeros((b_n, rx_n, ra_n, tout), f32)
+    yy = np.zeros((b_n, rx_n, ra_n, tout), f32)
+    bi = np.arange(b_n)[:, None, None, None]
+    for t0 in range(0, tout, 256):
+        nt = min(256, tout - t0)
+        tl = np.arange(nt)
+        t = t0 + tl
+        lo = np.maximum(t - (tn - 1), 0)
+        hi = np.minimum(t, L - 1)
+        if mutation == "hi_short":
+            hi = hi - 1
+        if mutation == "lo_late":
+            lo = lo + 1
+        if mutation == "lo_early":
+            lo = np.maximum(t - tn, 0)
+        re = np.zeros((b_n, rx_n, ra_n, nt), f32)
+        im = np.zeros((b_n, rx_n, ra_n, nt), f32)
+        for tx in range(tx_n):
+            sc = None
+            if link_scale is not None:
+                stx = (tx + 1) % tx_n if mutation == "scale_other_tx" else tx
+                sc = np.asarray(link_scale, f32)[:, :, stx][:, :, None, None]
+            for ta in range(ta_n):
+                hs = hf[:, :, :, tx, ta, t0 * L:t0 * L + nt * L]                 # the stage: cnt = nt * L contiguous values
+                for l in range(L):
+                    on = (l >= lo) & (l <= hi)
+                    hv = hs[..., tl * L + l]
+                    hvx, hvy = hv.real, hv.imag
+                    if sc is not None:
+                        hvx, hvy = hvx * sc, hvy * sc
+                    xi = (bi * tx_n * ta_n + tx * ta_n + ta) * tn + np.maximum(t - l + (1 if mutation == "x_shift" else 0), 0)
+                    xi = np.minimum(np.broadcast_to(xi, (b_n, 1, 1, nt)), xf.size - 1)   # (lanes outside the window read nothing)
+                    xvx, xvy = xfx[xi], xfy[xi]
+                    re = np.where(on, re + (hvx * xvx - hvy * xvy), re)
+                    im = np.where(on, im + (hvx * xvy + hvy * xvx), im)
+        assert re.dtype == f32 and im.dtype == f32
+        yx[..., t0:t0 + nt], yy[..., t0:t0 + nt] = re, im
+    y = np.empty((b_n, rx_n, ra_n, tout), np.complex64)
+    y.real, y.imag = yx, yy
+    return y
