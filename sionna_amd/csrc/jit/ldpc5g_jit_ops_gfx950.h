@@ -42,20 +42,6 @@ JIT_DEV M64 m_not(M64 a) { return !a; }
 JIT_DEV M64 m_xor_c(M64 a, bool c) { return a != c; }
 JIT_DEV unsigned u_sel(M64 m, unsigned a, unsigned b) { return m ? a : b; }
 JIT_DEV unsigned u_div(unsigned a, unsigned d) { return a / d; }
-// f_eq / f_sel_m: a comparison whose lane mask is consumed several instructions later.  Written as volatile assembly so that the
-// order of the generated text is the order of the instructions: the compiler's scheduler moves a v_cmp next to the v_cndmask that
-// reads its mask (shortest scalar live range) and then has to pad the two wait states gfx950 wants between them with s_nop.
-typedef unsigned long long M64S;
-JIT_DEV M64S f_eq_abs(F32 a, F32 b) {                        // |a| == b
-  M64S m;
-  asm volatile("v_cmp_eq_f32_e64 %0, |%1|, %2" : "=s"(m) : "v"(a), "v"(b));
-  return m;
-}
-JIT_DEV F32 f_sel_m(M64S m, F32 a, F32 b) {                 // m ? a : b
-  F32 r;
-  asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-  return r;
-}
 JIT_DEV U32 u_shl(U32 a, int n) { return a << n; }
 JIT_DEV U32 u_shr(U32 a, int n) { return a >> n; }
 JIT_DEV F32 g_ld(const float* row, U32 voff, unsigned coff) { return *(const float*)((const char*)row + (voff + coff)); }
@@ -90,23 +76,6 @@ JIT_DEV U32 u_here(U32 a) {
   asm volatile("" : "+v"(a));
   return a;
 }
-// a ^ 256, computed where it is written (volatile: not hoisted out of the iteration loop into a long-lived register)
-JIT_DEV U32 u_xor256_here(U32 a) {
-  U32 r;
-  asm volatile("v_xor_b32_e32 %0, 0x100, %1" : "=v"(r) : "v"(a));
-  return r;
-}
-// a ^ 4 / a & ~4 (the other half of an 8-byte slot / the slot itself), computed where written
-JIT_DEV U32 u_xor4_here(U32 a) {
-  U32 r;
-  asm volatile("v_xor_b32_e32 %0, 4, %1" : "=v"(r) : "v"(a));
-  return r;
-}
-JIT_DEV U32 u_andn4_here(U32 a) {
-  U32 r;
-  asm volatile("v_and_b32_e32 %0, 0xfffffffb, %1" : "=v"(r) : "v"(a));
-  return r;
-}
 // inside an if-block on a wave-uniform condition: keeps it a branch (the optimiser would turn the block into selections
 // executed on every path)
 #define JIT_KEEP_BRANCH() asm volatile("" ::: "memory")
@@ -138,11 +107,9 @@ JIT_DEV void f_pk_addc(F32& d0, F32& d1, F32 a0, F32 a1, float c) {
 }
 #define JIT_TABLE __device__ const
 JIT_DEV void jit_tab_lane(F32& a, F32& b, const float (*tab)[2]) { a = tab[threadIdx.x & 63u][0]; b = tab[threadIdx.x & 63u][1]; }
-JIT_DEV F32 f_frexp_exp(F32 x) { return (float)__builtin_amdgcn_frexp_expf(x); }      // exponent e + 1 of a normal x, as a float
 JIT_DEV F32 f_min(F32 a, float b) { return __builtin_fminf(a, b); }
 JIT_DEV U32 u_and_or(U32 a, unsigned m, unsigned o) { return (a & m) | o; }
-JIT_DEV U32 u_msb_if_neg(F32 v) { return (v < 0.f) ? 0x80000000u : 0u; }
-JIT_DEV U32 u_msb_nonzero(F32 v) { return __builtin_bit_cast(unsigned, v) & 0x80000000u; }   // = u_msb_if_neg for every v but -0
+JIT_DEV U32 u_msb_nonzero(F32 v) { return __builtin_bit_cast(unsigned, v) & 0x80000000u; }   // "v < 0" for every v but -0
 // the message image of a workgroup pass between LDS and a caller's buffer (state variant): the calling wave's share, 8 bytes
 // per lane and step; rank / nranks = this wave among the waves that copy
 JIT_DEV void jit_copy_g2l(const float* g, unsigned lds_byte, unsigned nbytes, int rank, int nranks) {

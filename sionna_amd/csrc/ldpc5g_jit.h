@@ -48,41 +48,13 @@ struct JitGeometry {
   size_t ws_bytes = 0;   // bytes of one workgroup's workspace row
 };
 
-// development knobs of the generator (SAMD_JIT_* options, read when the source is generated)
 struct JitState;
 
-struct JitKnobs {
-  int pipe = 1;        // items whose loads are in flight (1: load - update - store per item)
-  int xor128 = 0;      // Z = 128: second chunk's block position recomputed in the loop (v_xor) instead of a register
-  int layout = 1;      // 1 (Z = 128 only): the two chunks of an edge block interleaved (8-byte DS instructions in both phases)
-  int prefetch = 0;    // next codeword's channel LLRs requested one codeword ahead.  Round 5: on (+).  End of round 6: OFF - the
-                       // values wait in ~40 registers through a whole decode (23 -> 4 spilled registers without them); C2 min-sum
-                       // 15.58 -> 15.28 ms, boxplus-phi unchanged, the other codes of the sweep -0.5 ... +4.5 % (profiles/r06zy)
-  int prio = 1;        // s_setprio per item
-  int vnrev = -1;      // VN lists assigned to the waves in reverse order (-1: by generator - 0 for the levelled Z = 128 schedule, else 1)
-  int sched = -1;      // -1: by layout (interleaved 1, planar 0).  0: the generic kernel's lists (tuned on hardware over rounds 2-3: cut items, SIMD-aware order);
-                       // 1: an own longest-processing-time assignment by instruction counts - measured 4-7 % slower
-                       // for every cost model tried (profiles/r05c_jit_sched_sweep.txt): an item's cost is its latency
-                       // chain, not its instruction count
-  int rotate = -1;     // a wave's item order rotated by its index on its SIMD (-1: by generator - 0 for the levelled Z = 128 schedule, else 1)
-  int cn_slope = 10, cn_ovh = -1, cn_fused = 6, vn_slope = 8, vn_ovh = 10, vn_pair_max = -1;   // cost model (-1: by layout)
-  int cn_pair_max = 32;   // rows of higher degree are two single-chunk items
-  int waves = 0;          // own schedule (sched = 1): waves per workgroup, 0 = the generic kernel's 16
-  int cmp_ahead = 0;      // min-sum check node: comparisons issued this many edges ahead of the selections that read them
-  int phi_rolled = 1;     // boxplus-phi: the check-node loops over a row's edges rolled (one phi body per pass) instead of unrolled
-  int general = 0;        // 1: the any-lifting-size programs also for the codes of the Z = 128 class (A/B)
-  int group = 0, wgs = 0; // any-lifting-size programs: codewords per workgroup / workgroups per CU (0: chosen by the generator)
-  int pairx = -1;         // -1: by the generator; 0 / 1: pairs inside a codeword / across two codewords
-  int spill = 1;          // codes beyond LDS: the last base rows' blocks in an L2 workspace row (0: such codes keep the generic engines)
-  int a1 = 1;             // plain min-sum: no clip of the smallest magnitude (it cannot exceed llr_max; JIT_A1_NOCLIP)
-  int phi_tab0 = 1;       // boxplus-phi: table of the logarithm at LDS address 0 (no v_or per lookup)
-  int phi_tab32 = 1;      // boxplus-phi: the table as two planes read with 4-byte loads (no register moves; JIT_PHI_TAB32)
-  int phi_lean = 1;       // boxplus-phi: clamp as one v_med3 with |x| folded, sign of a v2c from its sign bit (a v2c is never -0)
-  int simdbal = 1;        // Z = 128 class: items exchanged between waves of different SIMDs to level the per-SIMD instruction sums
-  int state = 0;          // the variant that takes / returns the message image of a workgroup pass (return_state / msg_v2c; set by the caller)
-  int vst32 = 0;          // Z = 128 class: variable-node results stored in node order by two 4-byte stores (JIT_VN_ST32, templates)
-  int abl = 0;         // -DSAMD_DEV builds: SAMD_JIT_ABL (see jit/ldpc5g_jit_templates.h)
-  void capture();
+// which form of a code's kernel is generated.  Everything else about the programs - schedule, message layout, lane geometry,
+// the form of each node update - follows from the code and the rule alone (ldpc5g_jit.cpp).
+struct JitVariant {
+  int state = 0;   // takes / returns the message image of a workgroup pass (return_state / msg_v2c)
+  int abl = 0;     // -DSAMD_DEV builds: SAMD_JIT_ABL, parts of an iteration removed (see jit/ldpc5g_jit_templates.h)
 };
 
 // true when the code is in the class the generator covers (see jit_eligible in ldpc5g_jit.cpp)
@@ -90,7 +62,7 @@ bool jit_eligible(const samd_ldpc5g* h);
 // the whole translation unit handed to hipRTC.  with_ops = false: without the gfx950 operation definitions and the
 // __global__ entry (what tests/jit_emu compiles for the CPU)
 // rule: 0 offset-min-sum, 1 min-sum, 2 boxplus-phi on the defined exp / log
-std::string jit_generate_source(const samd_ldpc5g* h, int return_infobits, int rule, bool with_ops, const JitKnobs& knobs);
+std::string jit_generate_source(const samd_ldpc5g* h, int return_infobits, int rule, bool with_ops, JitVariant variant);
 // SAMD_OK, SAMD_ERR_UNSUPPORTED (caller runs the generic kernel) or an error
 int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
                       float llr_max, float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes,
@@ -100,8 +72,8 @@ size_t jit_workspace_bytes(const samd_ldpc5g* h, int batch, int cn_mode);
 // graph data of the generator for a code that build_onchip_bp_tables left without a plan (any even lifting size)
 void build_jit_plan_general(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
 // 0: no generated kernel; 1: the Z = 128 k class (whole chunks of one kind, constants); 2: any-lifting-size programs
-int jit_class(const samd_ldpc5g* h, const JitKnobs& kn, bool phi);
-bool jit_geometry(const samd_ldpc5g* h, const JitKnobs& kn, bool phi, JitGeometry* g);
+int jit_class(const samd_ldpc5g* h, bool phi);
+bool jit_geometry(const samd_ldpc5g* h, bool phi, JitGeometry* g);
 JitState* new_jit_state();
 void free_jit(samd_ldpc5g* h);
 

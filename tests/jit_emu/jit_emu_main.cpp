@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: runs the per-wave programs libsionna_amd.so generated for one 5G LDPC code (JIT_EMU_SRC, written by
-// tests/test_jit_emu.py from samd_ldpc5g_jit_source) on the CPU - JIT_NWAVES host threads = the waves of a workgroup (16 unless SAMD_JIT_WAVES says otherwise), one
+// tests/test_jit_emu.py from samd_ldpc5g_jit_source) on the CPU - JIT_NWAVES host threads = the waves of a workgroup (16, 8 or 4 by the generator's lane geometry), one
 // workgroup after the other.  See jit_emu_ops.h.
 #include "jit_emu_ops.h"
 #include JIT_EMU_SRC

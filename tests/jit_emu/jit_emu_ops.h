@@ -105,7 +105,6 @@ JIT_DEV F32 f_sel(const M64& m, const F32& a, const F32& b) {
   for (int i = 0; i < 64; ++i) r.v[i] = m.v[i] ? a.v[i] : b.v[i];
   return r;
 }
-typedef M64 M64S;
 struct JitEmuExec {
   bool saved[64];
   explicit JitEmuExec(const M64& m) {
@@ -153,12 +152,6 @@ JIT_DEV U32 u_div(const U32& a, unsigned d) {
   for (int i = 0; i < 64; ++i) r.v[i] = a.v[i] / d;
   return r;
 }
-JIT_DEV M64S f_eq_abs(const F32& a, const F32& b) {
-  M64 r;
-  for (int i = 0; i < 64; ++i) r.v[i] = fabsf(a.v[i]) == b.v[i];
-  return r;
-}
-JIT_DEV F32 f_sel_m(const M64S& m, const F32& a, const F32& b) { return f_sel(m, a, b); }
 JIT_DEV U32 u_shl(const U32& a, int n) {
   U32 r;
   for (int i = 0; i < 64; ++i) r.v[i] = a.v[i] << n;
@@ -261,9 +254,6 @@ JIT_DEV U32 u_min(const U32& a, const U32& b) {
   return r;
 }
 JIT_DEV U32 u_here(const U32& a) { return a; }
-JIT_DEV U32 u_xor256_here(const U32& a) { return a ^ U32(256u); }
-JIT_DEV U32 u_xor4_here(const U32& a) { return a ^ U32(4u); }
-JIT_DEV U32 u_andn4_here(const U32& a) { return a & U32(0xfffffffbu); }
 #define JIT_KEEP_BRANCH() do { } while (0)
 JIT_DEV U32 u_xor3(const U32& a, const U32& b, const U32& c) { return a ^ b ^ c; }
 JIT_DEV U32 u_xor_and(const U32& m, const U32& v, unsigned k) { return m ^ (v & U32(k)); }
@@ -289,22 +279,12 @@ JIT_DEV void f_pk_addc(F32& d0, F32& d1, const F32& a0, const F32& a1, float c) 
 JIT_DEV void jit_tab_lane(F32& a, F32& b, const float (*tab)[2]) {
   for (int i = 0; i < 64; ++i) { a.v[i] = tab[i][0]; b.v[i] = tab[i][1]; }
 }
-JIT_DEV F32 f_frexp_exp(const F32& x) {
-  F32 r;
-  for (int i = 0; i < 64; ++i) { unsigned b; memcpy(&b, &x.v[i], 4); r.v[i] = (float)((int)((b >> 23) & 0xffu) - 126); }
-  return r;
-}
 JIT_DEV F32 f_min(const F32& a, float b) {
   F32 r;
   for (int i = 0; i < 64; ++i) r.v[i] = fminf(a.v[i], b);
   return r;
 }
 JIT_DEV U32 u_and_or(const U32& a, unsigned m, unsigned o) { return (a & U32(m)) | U32(o); }
-JIT_DEV U32 u_msb_if_neg(const F32& v) {
-  U32 r;
-  for (int i = 0; i < 64; ++i) r.v[i] = (v.v[i] < 0.f) ? 0x80000000u : 0u;
-  return r;
-}
 JIT_DEV U32 u_msb_nonzero(const F32& v) {                      // the sign bit; the generated code relies on "never -0": checked here
   U32 r;
   for (int i = 0; i < 64; ++i) {

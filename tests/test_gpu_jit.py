@@ -65,7 +65,7 @@ GENERAL_CODES = [(768, 1536, None, 2), (1024, 2048, "bg1", None), (100, 200, Non
 @pytest.mark.parametrize("grid", [None, "2"])
 def test_specialised_kernel_bit_exact_vs_oracle(phy, k, n, bg, m, grid):
     """small batches through the specialised kernel (SAMD_LDPC_JIT=2: any batch size); grid = 2 workgroups: each decodes
-    several codewords in sequence (the codeword loop with its prefetch of the next codeword's channel values)"""
+    several codewords in sequence (the codeword loop with its loads of each codeword's channel values)"""
     code = LDPC5GCode(k, n, m, bg)
     llr = _noisy_llr(code, 7 if (k, n, bg, m) in CODES else 150, k + n)    # (several groups of codewords per workgroup)
     llr[0, :7] = 0
@@ -86,11 +86,9 @@ def test_specialised_kernel_bit_exact_vs_oracle(phy, k, n, bg, m, grid):
         assert np.array_equal(_np(dec(llr)), (0 >= -ref).astype(np.float32))
 
 
-@pytest.mark.parametrize("opts", [{"SAMD_JIT_LAYOUT": "1"}, {"SAMD_JIT_LAYOUT": "1", "SAMD_JIT_PIPE": "2", "SAMD_JIT_PREFETCH": "0"},
-                                  {"SAMD_JIT_SCHED": "1", "SAMD_JIT_PIPE": "2", "SAMD_JIT_XOR128": "1"}, {"SAMD_JIT_CMP_AHEAD": "2"}])
-def test_generator_variants_bit_exact(phy, opts):
-    """the generator's other forms of the C2 kernel (interleaved message layout with 8-byte DS instructions, own schedule,
-    pipelined loads, xor positions): the same soft outputs as the oracle"""
+def test_c2_kernel_two_workgroups_bit_exact(phy):
+    """the C2 kernel (interleaved message layout with 8-byte DS instructions, own schedule) on nine codewords and two workgroups,
+    min-sum with information bits and offset-min-sum with the codeword: the same soft outputs as the oracle"""
     import contextlib
     k, n, m, bg = 2816, 8448, 6, "bg1"
     code = LDPC5GCode(k, n, m, bg)
@@ -100,28 +98,25 @@ def test_generator_variants_bit_exact(phy, opts):
     with contextlib.ExitStack() as st:
         st.enter_context(_opt("SAMD_LDPC_JIT", "2"))
         st.enter_context(_opt("SAMD_ONCHIP_GRID", "2"))
-        for kk, vv in opts.items():
-            st.enter_context(_opt(kk, vv))
         enc = phy.fec.ldpc.LDPC5GEncoder(k, n, num_bits_per_symbol=m, bg=bg)
         for cn, it, infobits in (("minsum", 7, True), ("offset-minsum", 4, False)):
             dec = phy.fec.ldpc.LDPC5GDecoder(enc, cn_update=cn, hard_out=False, return_infobits=infobits, num_iter=it)
             before = _launches(enc, dec)
             got = _np(dec(llr))
             assert _launches(enc, dec) == before + 1
-            assert np.array_equal(got, _reference(code, llr, cn, it, infobits, m)), (cn, opts)
+            assert np.array_equal(got, _reference(code, llr, cn, it, infobits, m)), cn
 
 
-@pytest.mark.parametrize("k,n,bg,m,rolled", [(2816, 8448, "bg1", 6, "1"), (2816, 8448, "bg1", 6, "0"), (768, 1536, None, 2, "1"),
-                                             (1024, 2048, "bg1", None, "1"), (1234, 2468, None, 4, "0")])
-def test_boxplus_phi_on_the_generated_kernel_bit_exact(phy, k, n, bg, m, rolled):
-    """the defined phi of round 5 inside a generated kernel - round 6: check-node loops rolled (the default; the unrolled form
-    stays selectable), every even lifting size: soft outputs array_equal to the oracle, both output forms"""
+@pytest.mark.parametrize("k,n,bg,m", [(2816, 8448, "bg1", 6), (768, 1536, None, 2), (1024, 2048, "bg1", None), (1234, 2468, None, 4)])
+def test_boxplus_phi_on_the_generated_kernel_bit_exact(phy, k, n, bg, m):
+    """the defined phi of round 5 inside a generated kernel - round 6: check-node loops rolled, every even lifting size: soft
+    outputs array_equal to the oracle, both output forms"""
     import contextlib
     code = LDPC5GCode(k, n, m, bg)
     llr = _noisy_llr(code, 6 if k == 2816 else 50, 7, sigma=0.7)
     llr[0, :9] = 0
     with contextlib.ExitStack() as st:
-        for kk, vv in (("SAMD_LDPC_JIT", "2"), ("SAMD_JIT_PHI_ROLLED", rolled), ("SAMD_ONCHIP_GRID", "2")):
+        for kk, vv in (("SAMD_LDPC_JIT", "2"), ("SAMD_ONCHIP_GRID", "2")):
             st.enter_context(_opt(kk, vv))
         enc = phy.fec.ldpc.LDPC5GEncoder(k, n, num_bits_per_symbol=m, bg=bg)
         for it, infobits in ((1, True), (6, False)):

@@ -125,7 +125,7 @@ def main():
     ap.add_argument("--infobits", type=int, default=1)
     ap.add_argument("--cn", default="minsum", choices=["minsum", "offset-minsum", "boxplus-phi"])
     ap.add_argument("--out", default="/tmp/jit")
-    ap.add_argument("--opt", action="append", default=[], help="SAMD_JIT_*=value (repeatable)")
+    ap.add_argument("--opt", action="append", default=[], help="library option NAME=value, e.g. SAMD_JIT_STATE=1 for the state variant or a SAMD_LDPC_JIT* policy option (repeatable)")
     a = ap.parse_args()
     from sionna_amd import _ffi
     for kv in a.opt:
