@@ -169,6 +169,24 @@ int samd_ldpc5g_decode_layered_f32(const samd_ldpc5g_t* h, const float* llr, flo
                                    float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* The same call (decoding.py:1383-1390, _bp_iter with an array schedule :463-520, vn_update_sum :681-732, min-sum node
+ * updates :755-953, rate recovery and output mapping :1427-1536) in the textbook layered form, SAMD_CN_MINSUM /
+ * SAMD_CN_OFFSET_MINSUM only: one running total per variable node, t = xtot - c_old, v2c = clip(t), xtot = t + c_new, each edge
+ * touched once per layer; 12 bytes of LDS per check node (two sent magnitudes, sign bits and the index of the minimum) instead
+ * of 4 per edge, several codewords per workgroup, no workspace (..._workspace_bytes is 0).  The same function as the entry
+ * above in exact arithmetic, NOT the same float32 bits: its bits are those of tests/ldpc_layered_rt_f32.py.  Opt-in
+ * (LDPC5GDecoder.layered_totals = "running").  ..._supported: min-sum family, no partially pruned base row, state fits LDS;
+ * Same argument lists as the entries above.
+ * ..._slots: how many codewords one workgroup decodes side by side (0: not supported) - the batch granule of this engine.  The
+ * codewords of a workgroup share its barriers, so a batch that is no multiple of it leaves one workgroup with idle slots for a
+ * whole decode: a caller that forms its own batches (a link simulation's Monte-Carlo loop) rounds them to a multiple. */
+int samd_ldpc5g_decode_layered_rt_supported(const samd_ldpc5g_t* h, int cn_mode);
+size_t samd_ldpc5g_decode_layered_rt_workspace_bytes(const samd_ldpc5g_t* h, int batch);
+int samd_ldpc5g_decode_layered_rt_slots(const samd_ldpc5g_t* h);
+int samd_ldpc5g_decode_layered_rt_f32(const samd_ldpc5g_t* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
+                                      float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* Whole LDPC5GDecoder.call on chip: rate recovery + num_iter flooding BP iterations +
  * output mapping in ONE kernel, one codeword per workgroup, messages resident in LDS.
  *   One float per edge in LDS (engine 2) when the code's E messages x 4 B fit in 160 KB - n=8448 rate 1/3

@@ -104,6 +104,10 @@ _SIGNATURES = {
     "samd_ldpc5g_decode_layered_supported": (_i32, [_vp, _i32]),
     "samd_ldpc5g_decode_layered_workspace_bytes": (_sz, [_vp, _i32]),
     "samd_ldpc5g_decode_layered_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, _sz, _vp]),
+    "samd_ldpc5g_decode_layered_rt_supported": (_i32, [_vp, _i32]),
+    "samd_ldpc5g_decode_layered_rt_workspace_bytes": (_sz, [_vp, _i32]),
+    "samd_ldpc5g_decode_layered_rt_slots": (_i32, [_vp]),
+    "samd_ldpc5g_decode_layered_rt_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, _sz, _vp]),
     "samd_ldpc5g_jit_supported": (_i32, [_vp]),
     "samd_ldpc5g_jit_prepare": (_i32, [_vp, _i32, _i32]),
     "samd_ldpc5g_jit_source": (C.c_long, [_vp, _i32, _i32, _i32, _vp, _sz]),

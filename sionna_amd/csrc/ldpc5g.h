@@ -134,6 +134,29 @@ int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int ba
                       float llr_max, float offset, int hard_out, int return_infobits, void* workspace,
                       size_t workspace_bytes, hipStream_t st);
 
+// Groups of consecutive base rows that share no column (both layered engines): the updates of a group's rows commute, so
+// one step of the schedule takes a whole group.  col_private marks columns that belong to one row alone (degree-1 columns
+// of the extension part), which never make two rows clash.  single: every row its own group (development).
+inline std::vector<std::vector<int>> layered_row_groups(const BaseRows& by_row, int ncu, int nb,
+                                                        const std::vector<char>& col_private, bool single) {
+  std::vector<std::vector<int>> groups;
+  std::vector<char> used(nb, 0);
+  std::vector<int> cur;
+  for (int r = 0; r < ncu; ++r) {
+    bool clash = false;
+    for (auto& e : by_row[r]) clash = clash || (!col_private[e.first] && used[e.first]);
+    if ((clash && !cur.empty()) || single) {
+      if (!cur.empty()) groups.push_back(cur);
+      cur.clear();
+      std::fill(used.begin(), used.end(), 0);
+    }
+    cur.push_back(r);
+    for (auto& e : by_row[r]) used[e.first] = 1;
+  }
+  if (!cur.empty()) groups.push_back(cur);
+  return groups;
+}
+
 // ---- on-chip layered decoder (ldpc5g_onchip_ly.hip): record lists per wave, row / column edge tables
 struct Ldpc5gLayered {
   int ok = 0, lds_bytes = 0, msg_floats = 0, n_ext = 0, groups = 0, zero_off = 0, waves = 16, bp_lds_bytes = 0;
@@ -143,6 +166,16 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row);
 size_t onchip_ly_workspace_bytes(const samd_ldpc5g* h, int batch);
 int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode, float llr_max,
                      float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes, hipStream_t st);
+
+// ---- on-chip layered decoder with running totals, min-sum family (ldpc5g_onchip_lyrt.hip): per step (group of rows) a
+// list of check-node items, `slots` codewords per workgroup walking it in lockstep
+struct Ldpc5gLayeredRt {
+  int ok = 0, slots = 0, slot_bytes = 0, waves = 0, wg_per_cu = 0, steps = 0;
+  DeviceTable<int32_t> step_ptr, items, ent_tab;
+};
+int build_onchip_lyrt_tables(samd_ldpc5g* h, const BaseRows& by_row);
+int launch_onchip_lyrt(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode, float llr_max,
+                       float offset, int hard_out, int return_infobits, hipStream_t st);
 }  // namespace samd
 
 struct samd_ldpc5g {
@@ -160,6 +193,7 @@ struct samd_ldpc5g {
   samd::Ldpc5gMs ms;
   samd::Ldpc5gSpill sp;
   samd::Ldpc5gLayered ly;
+  samd::Ldpc5gLayeredRt lyrt;
 };
 
 namespace samd {

@@ -451,6 +451,7 @@ extern "C" int samd_ldpc5g_create(int bg, int z, const int16_t* rows, const int1
   if (rc == SAMD_OK) rc = build_onchip_bp_tables(h, by_row);
   if (rc == SAMD_OK) rc = build_onchip_mss_tables(h, by_row);
   if (rc == SAMD_OK) rc = build_onchip_ly_tables(h, by_row);
+  if (rc == SAMD_OK) rc = build_onchip_lyrt_tables(h, by_row);
   if (rc != SAMD_OK) { samd_ldpc5g_destroy(h); return rc; }
   build_jit_plan_general(h, by_row);                       // graph data for the generated kernel of any other code
   if (h->jit_plan) h->jit_state = new_jit_state();
@@ -589,6 +590,39 @@ extern "C" int samd_ldpc5g_decode_layered_f32(const samd_ldpc5g_t* h, const floa
   SAMD_REQUIRE(h && llr && out && batch > 0 && num_iter >= 0, "bad argument");
   return launch_onchip_ly(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, workspace,
                           workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- the same schedule with running totals (textbook layered form), min-sum family: ldpc5g_onchip_lyrt.hip.  Opt-in
+// (LDPC5GDecoder.layered_totals = "running"): its float32 rounding is that of tests/ldpc_layered_rt_f32.py, not the oracle's.
+extern "C" int samd_ldpc5g_decode_layered_rt_supported(const samd_ldpc5g_t* h, int cn_mode) {
+  const bool rule = cn_mode == SAMD_CN_MINSUM || cn_mode == SAMD_CN_OFFSET_MINSUM;
+  return (h && h->lyrt.ok && rule && !h->opt.no_onchip_layered) ? 1 : 0;   // SAMD_NO_ONCHIP_LAYERED: both layered engines off
+}
+
+extern "C" size_t samd_ldpc5g_decode_layered_rt_workspace_bytes(const samd_ldpc5g_t* h, int batch) {
+  (void)h; (void)batch;
+  return 0;                                                // the whole state lives in LDS
+}
+
+extern "C" int samd_ldpc5g_decode_layered_rt_slots(const samd_ldpc5g_t* h) {
+  return (h && h->lyrt.ok && !h->opt.no_onchip_layered) ? h->lyrt.slots : 0;
+}
+
+extern "C" int samd_ldpc5g_decode_layered_rt_f32(const samd_ldpc5g_t* h, const float* llr, float* out, int batch, int num_iter,
+                                                 int cn_mode, float llr_max, float offset, int hard_out, int return_infobits,
+                                                 void* workspace, size_t workspace_bytes, void* stream) {
+  (void)workspace; (void)workspace_bytes;
+  SAMD_REQUIRE(h && llr && out && batch > 0 && num_iter >= 0, "bad argument");
+  SAMD_REQUIRE(!h->host_only, "handle was built without a device (SAMD_HOST_ONLY)");
+  if (!samd_ldpc5g_decode_layered_rt_supported(h, cn_mode)) {
+    set_error("layered running-total engine: code or rule not covered");
+    return SAMD_ERR_UNSUPPORTED;
+  }
+  if (!minsum_envelope_ok(h, llr_max)) {                   // the guard of samd_ldpc5g_decode_f32's min-sum kernels
+    set_error("code / llr_max outside the on-chip decoder's envelope");
+    return SAMD_ERR_UNSUPPORTED;
+  }
+  return launch_onchip_lyrt(h, llr, out, batch, num_iter, cn_mode, llr_max, offset, hard_out, return_infobits, (hipStream_t)stream);
 }
 
 extern "C" int samd_ldpc5g_decode_engine(const samd_ldpc5g_t* h, int cn_mode) {

@@ -438,23 +438,7 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
     if (col_deg[c] == 1 && sft == 0 && d >= 3 && d <= 10) { fused_col[r] = c; col_fused[c] = 1; ext_of_row[r] = n_ext++; }
   }
   // groups of consecutive rows that share no non-fused column
-  std::vector<std::vector<int>> groups;
-  {
-    std::vector<char> used(h->nb, 0);
-    std::vector<int> cur;
-    for (int r = 0; r < ncu; ++r) {
-      bool clash = false;
-      for (auto& e : by_row[r]) clash = clash || (!col_fused[e.first] && used[e.first]);
-      if ((clash && !cur.empty()) || opt_set("SAMD_LY_NOGROUP")) {
-        if (!cur.empty()) groups.push_back(cur);
-        cur.clear();
-        std::fill(used.begin(), used.end(), 0);
-      }
-      cur.push_back(r);
-      for (auto& e : by_row[r]) used[e.first] = 1;
-    }
-    if (!cur.empty()) groups.push_back(cur);
-  }
+  const std::vector<std::vector<int>> groups = layered_row_groups(by_row, ncu, h->nb, col_fused, opt_set("SAMD_LY_NOGROUP"));
   const int G = (int)groups.size();
   std::vector<std::vector<char>> in_group(G, std::vector<char>(h->nb, 0));
   for (int g = 0; g < G; ++g)

@@ -10,7 +10,8 @@ HIP engines behind the same Block API (the library picks per code and rule, ``sa
 * 5G on-chip, flooding: ``samd_ldpc5g_decode_f32`` - rate recovery + all iterations + output mapping in ONE kernel
   with the messages in LDS (explicit messages csrc/ldpc5g_onchip_ms.inc, compressed check-node state
   csrc/ldpc5g_onchip.hip, part of the messages in L2 csrc/ldpc5g_onchip_mss.hip; min-sum family and boxplus rules);
-* 5G on-chip, ``cn_schedule="layered"``: ``samd_ldpc5g_decode_layered_f32`` (csrc/ldpc5g_onchip_ly.hip).
+* 5G on-chip, ``cn_schedule="layered"``: ``samd_ldpc5g_decode_layered_f32`` (csrc/ldpc5g_onchip_ly.hip); with
+  ``layered_totals = "running"``: ``samd_ldpc5g_decode_layered_rt_f32`` (csrc/ldpc5g_onchip_lyrt.hip).
 
 All use the arithmetic and summation order of oracle/ldpc_bp.py / oracle/ldpc_bp.c, which tests/test_oracle_ref_exec.py
 pins to the reference's own decoding.py executed under a NumPy stand-in for TensorFlow (min-sum family and VN update
@@ -374,6 +375,40 @@ class LDPC5GDecoder(LDPCBPDecoder):
 
     encoder = property(lambda self: self._encoder)
 
+    _layered_totals = "resum"
+    _layered_engine = None
+
+    @property
+    def layered_totals(self):
+        """How ``cn_schedule="layered"`` forms the variable-node totals (an addition to the reference's interface, settable
+        after construction).  ``"resum"`` (default): every touched variable node is re-summed after every layer - the
+        reference's float32 bits (csrc/ldpc5g_onchip_ly.hip).  ``"running"``: the textbook running total, ``t = xtot -
+        c_old; xtot = t + c_new`` (csrc/ldpc5g_onchip_lyrt.hip) - the same function in exact arithmetic, float32 rounding
+        as defined by tests/ldpc_layered_rt_f32.py, min-sum family on codes the engine covers; everything else runs as
+        with ``"resum"``."""
+        return self._layered_totals
+
+    @layered_totals.setter
+    def layered_totals(self, value):
+        if not isinstance(value, str) or value not in ("resum", "running"):
+            raise ValueError("layered_totals must be 'resum' or 'running'.")
+        self._layered_totals = value
+
+    @property
+    def layered_engine(self):
+        """Which engine the last layered ``call`` ran: "running" (ldpc5g_onchip_lyrt.hip), "resum" (ldpc5g_onchip_ly.hip),
+        "scheduled" (the HBM-resident scheduled engine) or None (no layered call yet)."""
+        return self._layered_engine
+
+    def _layered_onchip_wanted(self, double, msg_v2c):
+        """cn_schedule="layered" goes to an on-chip layered engine: float32, a built-in rule, no state in or out"""
+        return (self._layered5g and self._onchip_ok and not double and not self._custom and self._cn_mode in (1, 2, 3, 4)
+                and not self._return_state and msg_v2c is None)
+
+    def _layered_rt_wanted(self, double, msg_v2c):
+        """... and there the running-total engine is asked first: opted in, min-sum family"""
+        return self._layered_totals == "running" and self._cn_mode in (2, 3) and self._layered_onchip_wanted(double, msg_v2c)
+
     def build(self, input_shape, **kwargs):
         if input_shape[-1] != self._encoder.n:
             raise ValueError("Last dimension must be of length n.")
@@ -507,6 +542,23 @@ class LDPC5GDecoder(LDPCBPDecoder):
         _ffi.check(rc, "LDPC5GDecoder(on-chip layered)")
         return out
 
+    def _try_onchip_layered_rt(self, llr2d, num_iter):
+        """Whole layered decode with running totals in one kernel (csrc/ldpc5g_onchip_lyrt.hip); None when not covered."""
+        enc = self._encoder
+        lib, h = _ffi.lib(), enc._handle(self._nb_pruned_nodes)
+        if not lib.samd_ldpc5g_decode_layered_rt_supported(h, self._cn_mode):
+            return None
+        out_cols = enc.k if self._return_infobits else enc.n
+        out = torch.empty((llr2d.shape[0], out_cols), dtype=torch.float32, device=llr2d.device)
+        ws, ws_bytes = self._ws.get(lib.samd_ldpc5g_decode_layered_rt_workspace_bytes(h, llr2d.shape[0]))
+        rc = lib.samd_ldpc5g_decode_layered_rt_f32(
+            h, _ffi.ptr(llr2d), _ffi.ptr(out), llr2d.shape[0], int(num_iter), self._cn_mode, self._llr_max, self._offset,
+            int(self._hard_out), int(self._return_infobits), _ffi.ptr(ws), ws_bytes, _ffi.stream())
+        if rc == _ffi.ERR_UNSUPPORTED:
+            return None
+        _ffi.check(rc, "LDPC5GDecoder(on-chip layered, running totals)")
+        return out
+
     def call(self, llr_ch, /, *, num_iter=None, msg_v2c=None):
         enc = self._encoder
         if num_iter is None:
@@ -531,12 +583,18 @@ class LDPC5GDecoder(LDPCBPDecoder):
             res = self._try_onchip_state(llr2d, int(num_iter), msg_v2c)
             if res is not None:
                 return (res[0].reshape(out_shape), res[1]) if self._return_state else res[0].reshape(out_shape)
-        # cn_schedule="layered" (one sub-iteration per base row): the on-chip layered engine when the code is covered
-        if (self._layered5g and self._onchip_ok and not double and not self._custom and self._cn_mode in (1, 2, 3, 4)
-                and not self._return_state and msg_v2c is None and batch > 0):
-            out = self._try_onchip_layered(llr2d, num_iter)
+        # cn_schedule="layered" (one sub-iteration per base row): an on-chip layered engine when the code is covered
+        if self._layered_onchip_wanted(double, msg_v2c) and batch > 0:
+            out, engine = None, None
+            if self._layered_rt_wanted(double, msg_v2c):
+                out, engine = self._try_onchip_layered_rt(llr2d, num_iter), "running"
+            if out is None:
+                out, engine = self._try_onchip_layered(llr2d, num_iter), "resum"
             if out is not None:
+                self._layered_engine = engine
                 return out.reshape(out_shape)
+        if self._layered5g and batch > 0:
+            self._layered_engine = "scheduled"
 
         # generic engine: rate recovery -> BP -> output mapping (decoding.py:1431-1536)
         h = enc._handle(self._nb_pruned_nodes)
