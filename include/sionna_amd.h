@@ -68,6 +68,11 @@ int samd_debug_set_option(const char* key, const char* value);
 int samd_debug_options_generation(void);
 /* value of a switch: its length (copied NUL-terminated into buf when cap suffices), -1 when it is not set */
 long samd_debug_get_option(const char* key, char* buf, size_t cap);
+/* Development: 64-bit FNV-1a over every device table the calling thread has built since the last call (element size,
+ * count and bytes of each, in build order; samd_ldpc5g_create adds its engines' scalars), then reset.  It is kept for
+ * SAMD_HOST_ONLY handles too, which hold no table contents: tests/test_ldpc5g_selection.py holds the tables of a grid of
+ * codes to a record with it. */
+uint64_t samd_debug_table_digest(void);
 
 /* ------------------------------------------------------------------------------------
  * Generic LDPC flooding BP decoder (any parity-check matrix).

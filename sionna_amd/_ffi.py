@@ -200,6 +200,7 @@ _SIGNATURES = {
     "samd_debug_set_option": (_i32, [C.c_char_p, C.c_char_p]),
     "samd_debug_options_generation": (_i32, []),
     "samd_debug_get_option": (C.c_long, [C.c_char_p, C.c_char_p, _sz]),
+    "samd_debug_table_digest": (_u64, []),
 }
 
 

@@ -53,10 +53,24 @@ std::string opt_str(const char* key) {
   return it == r.kv.end() ? std::string() : it->second;
 }
 bool host_only() { return opt_set("SAMD_HOST_ONLY"); }
+
+static constexpr uint64_t kFnvOffset = 0xCBF29CE484222325ull, kFnvPrime = 0x100000001B3ull;
+static thread_local uint64_t g_table_digest = kFnvOffset;
+void table_digest_fold(const void* p, size_t bytes) {
+  const unsigned char* b = static_cast<const unsigned char*>(p);
+  uint64_t d = g_table_digest;
+  for (size_t i = 0; i < bytes; ++i) d = (d ^ b[i]) * kFnvPrime;
+  g_table_digest = d;
+}
 int opt_generation() { return registry().generation.load(std::memory_order_acquire); }
 }  // namespace samd
 
 extern "C" const char* samd_last_error(void) { return samd::g_last_error.c_str(); }
+extern "C" uint64_t samd_debug_table_digest(void) {
+  const uint64_t d = samd::g_table_digest;
+  samd::g_table_digest = samd::kFnvOffset;
+  return d;
+}
 extern "C" int samd_version(void) { return 102; }
 extern "C" int samd_device_count(void) {
   int n = 0;

@@ -45,6 +45,12 @@ inline int launch_status() {
 // a machine without a GPU.  Such a handle refuses every launch.
 bool host_only();
 
+// Development record of what the table builders produced (samd_debug_table_digest): a thread-local 64-bit FNV-1a.  Every
+// DeviceTable::assign folds its element size, its count and its bytes into it - also under SAMD_HOST_ONLY, where the
+// handle keeps no table contents - so a refactoring of a builder can be held to the tables of the commit before it
+// (tests/test_ldpc5g_selection.py) on a machine without a GPU.
+void table_digest_fold(const void* p, size_t bytes);
+
 // One hipMalloc'd array that its owner's destructor frees (move-only).  assign(): an empty table, or any table of a
 // SAMD_HOST_ONLY handle, stays null with SAMD_OK; a HIP error is reported through set_error as SAMD_ERR_HIP.
 template <typename T>
@@ -56,6 +62,9 @@ class DeviceTable {
   ~DeviceTable() { if (p_) (void)hipFree(p_); }
   int assign(const T* src, size_t n) {
     *this = DeviceTable();
+    const uint64_t shape[2] = {sizeof(T), n};
+    table_digest_fold(shape, sizeof(shape));
+    table_digest_fold(src, n * sizeof(T));
     if (n == 0 || host_only()) return SAMD_OK;
     SAMD_HIP_CHECK(hipMalloc((void**)&p_, n * sizeof(T)));
     SAMD_HIP_CHECK(hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice));

@@ -13,9 +13,9 @@
 // Development switches a handle captured when it was created (options.h): its launch paths read these, never the
 // environment, so a handle behaves the same for its whole life.
 struct samd_ldpc5g_opt {
-  bool enc_bytes = false, enc_persist = false, onchip_compressed = false, force_spill = false, no_spill = false;
-  bool no_onchip_layered = false, bp_engine = false, onchip_v1 = false, ms_nogroup = false, ms_noz128 = false;
-  int ms_var = 1, ms_ldsbar = 0, onchip_grid = 0, enc_dbg = 0;
+  bool enc_bytes = false, onchip_compressed = false, force_spill = false, no_spill = false;
+  bool no_onchip_layered = false, bp_engine = false, onchip_v1 = false;
+  int onchip_grid = 0, enc_dbg = 0;
   // boxplus-phi on the generated kernel (bit-identical).  Round 5, loops unrolled: SLOWER than the generic explicit-message
   // kernel (437 KB of code for 16 wave programs, 1076 spilled registers: 144.7 against 119.9 ms per 65536 C2 codewords).
   // Round 6, check-node loops rolled (jit_cn_phi_rolled): 113.0 ms at C2 (0.580 M against 0.546 M decodes/s), 1.5 - 2 x the
@@ -30,12 +30,10 @@ struct samd_ldpc5g_opt {
   int jit = 1, jit_min_batch = 256;
   void capture() {
     using samd::opt_set; using samd::opt_int;
-    enc_bytes = opt_set("SAMD_ENC_BYTES"); enc_persist = opt_set("SAMD_ENC_PERSIST");
+    enc_bytes = opt_set("SAMD_ENC_BYTES");
     onchip_compressed = opt_set("SAMD_ONCHIP_COMPRESSED"); force_spill = opt_set("SAMD_FORCE_SPILL");
     no_spill = opt_set("SAMD_NO_SPILL"); no_onchip_layered = opt_set("SAMD_NO_ONCHIP_LAYERED");
     bp_engine = opt_set("SAMD_BP_ENGINE"); onchip_v1 = opt_set("SAMD_ONCHIP_V1");
-    ms_nogroup = opt_set("SAMD_MS_NOGROUP"); ms_noz128 = opt_set("SAMD_MS_NOZ128");
-    ms_var = (int)opt_int("SAMD_MS_VAR", 1) & 1; ms_ldsbar = (int)opt_int("SAMD_MS_LDSBAR", 0);
     onchip_grid = (int)opt_int("SAMD_ONCHIP_GRID", 0);
     jit_phi = (int)opt_int("SAMD_LDPC_JIT_PHI", -1);
     jit = (int)opt_int("SAMD_LDPC_JIT", 1); jit_min_batch = (int)opt_int("SAMD_LDPC_JIT_MIN_BATCH", 256);
@@ -136,17 +134,17 @@ int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int ba
 
 // Groups of consecutive base rows that share no column (both layered engines): the updates of a group's rows commute, so
 // one step of the schedule takes a whole group.  col_private marks columns that belong to one row alone (degree-1 columns
-// of the extension part), which never make two rows clash.  single: every row its own group (development).
+// of the extension part), which never make two rows clash.
 inline std::vector<std::vector<int>> layered_row_groups(const BaseRows& by_row, int ncu, int nb,
-                                                        const std::vector<char>& col_private, bool single) {
+                                                        const std::vector<char>& col_private) {
   std::vector<std::vector<int>> groups;
   std::vector<char> used(nb, 0);
   std::vector<int> cur;
   for (int r = 0; r < ncu; ++r) {
     bool clash = false;
     for (auto& e : by_row[r]) clash = clash || (!col_private[e.first] && used[e.first]);
-    if ((clash && !cur.empty()) || single) {
-      if (!cur.empty()) groups.push_back(cur);
+    if (clash && !cur.empty()) {
+      groups.push_back(cur);
       cur.clear();
       std::fill(used.begin(), used.end(), 0);
     }
@@ -198,14 +196,10 @@ struct samd_ldpc5g {
 
 namespace samd {
 
-// longest-processing-time-first assignment of items to the waves of the workgroup.
-// cap (optional, one entry per wave): relative capacity of a wave - an item goes to the wave whose load / capacity
-// is smallest after taking it.  The SIMD arbiter serves its OLDEST wave first (measured with the trace build of
-// ldpc5g_onchip_ms.hip: of four equally loaded waves of a SIMD the first-launched finished a phase after 4.3 k
-// cycles, the last after 8.4 k - it mostly runs in the gaps of the older ones and then alone, latency-bound), so
-// waves that are launched later get less work.
+// longest-processing-time-first assignment of items to the waves of the workgroup: an item goes to the wave whose load
+// is smallest after taking it (the first such wave).
 inline void lpt_schedule(const std::vector<std::pair<int, int32_t>>& items, int nw, std::vector<int32_t>* ptr,
-                         std::vector<int32_t>* list, const std::vector<double>* cap = nullptr) {
+                         std::vector<int32_t>* list) {
   std::vector<size_t> order(items.size());
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return items[a].first > items[b].first; });
@@ -216,26 +210,16 @@ inline void lpt_schedule(const std::vector<std::pair<int, int32_t>>& items, int 
     int w = 0;
     double best = 0.0;
     for (int q = 0; q < nw; ++q) {
-      const double t = (load[q] + cost) / (cap ? (*cap)[q] : 1.0);
+      const double t = load[q] + cost;
       if (q == 0 || t < best) { best = t; w = q; }
     }
     per[w].push_back(items[i].second);
     load[w] += cost;
   }
-  // order of a wave's items (SAMD_MS_ORDER; default 2: +2.5 % at C2 - the four waves of a SIMD start a phase on items of
-  // different size instead of all on their largest): 0 = largest first on every wave; 1 = odd waves
-  // smallest first; 2 = rotated by the wave's index on its SIMD; 3 = waves 2, 3 (mod 4) smallest first
-  const int order_mode = (int)opt_int("SAMD_MS_ORDER", 2);       // handle-build time
-  for (int w = 0; w < nw && order_mode; ++w) {
-    if (per[w].size() < 2) continue;
-    if ((order_mode == 1 && (w & 1)) || (order_mode == 3 && (w & 2))) std::reverse(per[w].begin(), per[w].end());
-    if (order_mode == 2) std::rotate(per[w].begin(), per[w].begin() + ((w >> 2) % per[w].size()), per[w].end());
-    if (order_mode == 4 && ((w >> 2) & 1)) std::reverse(per[w].begin(), per[w].end());
-    if (order_mode == 5) std::rotate(per[w].begin(), per[w].begin() + (w % per[w].size()), per[w].end());
-    if (order_mode == 6) std::rotate(per[w].begin(), per[w].begin() + ((2 * (w >> 2)) % per[w].size()), per[w].end());
-    if (order_mode == 7) std::rotate(per[w].begin(), per[w].begin() + ((w & 3) % per[w].size()), per[w].end());
-    if (order_mode == 8) std::rotate(per[w].begin(), per[w].begin() + (((w >> 2) + (w & 3)) % per[w].size()), per[w].end());
-  }
+  // a wave's items, largest first, rotated by the wave's index on its SIMD: the four waves of a SIMD start a phase on
+  // items of different size instead of all on their largest (+2.5 % at C2 over largest first on every wave)
+  for (int w = 0; w < nw; ++w)
+    if (per[w].size() >= 2) std::rotate(per[w].begin(), per[w].begin() + ((w >> 2) % per[w].size()), per[w].end());
   ptr->assign(1, 0);
   list->clear();
   for (int w = 0; w < nw; ++w) {
@@ -250,11 +234,10 @@ inline void lpt_schedule(const std::vector<std::pair<int, int32_t>>& items, int 
 // therefore carries a priority 0..3 = the quarter of the phase's longest list that is still ahead of the wave; the
 // kernels apply it with s_setprio before the item (onchip_setprio), which turns the arbiter into "longest remaining
 // work first": the waves of a SIMD finish together (C2 min-sum: 2.10 -> 2.30 M decodes/s with the same lists).
-// items: (cost, id) as given to lpt_schedule; ptr / list: its result.  SAMD_MS_NOPRIO=1 disables (development).
+// items: (cost, id) as given to lpt_schedule; ptr / list: its result.
 inline std::vector<int> item_priorities(const std::vector<std::pair<int, int32_t>>& items, const std::vector<int32_t>& ptr,
                                         const std::vector<int32_t>& list) {
   std::vector<int> prio(list.size(), 0);
-  if (opt_set("SAMD_MS_NOPRIO")) return prio;
   auto cost_of = [&](int32_t id) {
     for (auto& it : items)
       if (it.second == id) return it.first + 3;

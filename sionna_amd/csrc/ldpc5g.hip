@@ -365,6 +365,18 @@ static size_t decode_lds_bytes(const samd_ldpc5g* h) {
   return ((size_t)2 * h->n_vn + (size_t)3 * h->n_cn) * 4 + 16;
 }
 
+// the scalar fields of every engine struct into the table digest (common.h), behind the tables their builders assigned
+static void digest_engine_scalars(const samd_ldpc5g* h) {
+  const int32_t s[] = {
+      h->max_dc, h->max_dv, h->base.n_cn_items, h->base.n_vn_items,
+      h->v2.ok, h->v2.ncu, h->v2.nbu, h->v2.dec_waves, h->v2.llr_global,
+      h->bp.ok, h->bp.waves, h->bp.llr_global, h->bp.edges, h->ms.tail_sh, h->ms.g_ok,
+      h->sp.ok, h->sp.lds_bytes, h->sp.g_floats, h->sp.spill_pct,
+      h->ly.ok, h->ly.lds_bytes, h->ly.msg_floats, h->ly.n_ext, h->ly.groups, h->ly.zero_off, h->ly.waves, h->ly.bp_lds_bytes,
+      h->lyrt.ok, h->lyrt.slots, h->lyrt.slot_bytes, h->lyrt.waves, h->lyrt.wg_per_cu, h->lyrt.steps};
+  table_digest_fold(s, sizeof(s));
+}
+
 }  // namespace samd
 
 using namespace samd;
@@ -455,6 +467,7 @@ extern "C" int samd_ldpc5g_create(int bg, int z, const int16_t* rows, const int1
   if (rc != SAMD_OK) { samd_ldpc5g_destroy(h); return rc; }
   build_jit_plan_general(h, by_row);                       // graph data for the generated kernel of any other code
   if (h->jit_plan) h->jit_state = new_jit_state();
+  digest_engine_scalars(h);
   *out = h;
   return SAMD_OK;
 }
@@ -476,7 +489,7 @@ extern "C" int samd_ldpc5g_encode_f32(const samd_ldpc5g_t* h, const float* bits,
     // one codeword per wave and launch slot: a wave that went on to a second codeword would wait for its own output
     // stores before the next input arrives (loads and stores share the in-order vmcnt counter) - measured 1.12 ms
     // against 0.28 ms (input + rows) + 0.42 ms (output) for the separate phases at C2
-    const int grid = h->opt.enc_persist ? std::min((batch + 3) / 4, 256 * 8 * 4) : (batch + 3) / 4;
+    const int grid = (batch + 3) / 4;
     hipLaunchKernelGGL(ldpc5g_encode_packed_kernel, dim3(grid), dim3(256), lds_p, (hipStream_t)stream, bits, out, make_rm(h),
                        batch, h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->base.row_ptr.get(), h->base.row_ent.get(),
                        h->base.enc_out_idx.get(), h->opt.enc_dbg);

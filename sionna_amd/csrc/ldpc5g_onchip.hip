@@ -399,22 +399,16 @@ int build_onchip_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   if (lds > 160 * 1024 && ((size_t)h->v2.nbu + (size_t)3 * (h->v2.ncu + 1)) * z * 4 <= 160 * 1024) {
     h->v2.llr_global = 1;                                          // channel LLRs move to the workspace (L2)
     lds = ((size_t)h->v2.nbu + (size_t)3 * (h->v2.ncu + 1)) * z * 4;
-  } else if (lds > 160 * 1024 && (size_t)3 * (h->v2.ncu + 1) * z * 4 <= 160 * 1024 && !opt_set("SAMD_NO_XTG")) {
+  } else if (lds > 160 * 1024 && (size_t)3 * (h->v2.ncu + 1) * z * 4 <= 160 * 1024) {
     h->v2.llr_global = 2;                                          // x_tot as well: LDS = check-node state only
     lds = (size_t)3 * (h->v2.ncu + 1) * z * 4;
-  } else if (lds > 160 * 1024 && (size_t)2 * (h->v2.ncu + 1) * z * 4 <= 160 * 1024 && !opt_set("SAMD_NO_XTG")) {
+  } else if (lds > 160 * 1024 && (size_t)2 * (h->v2.ncu + 1) * z * 4 <= 160 * 1024) {
     h->v2.llr_global = 3;                                          // ... and the sign words: LDS = (M1, M2)
     lds = (size_t)2 * (h->v2.ncu + 1) * z * 4;
   }
   h->v2.dec_waves = 16;
   for (int nwc : {8, 4, 2, 1})
     if (lds * (size_t)(kDecWaves / nwc) <= 160 * 1024) h->v2.dec_waves = nwc;
-  if (opt_set("SAMD_ONCHIP_WAVES")) {
-    const std::string e_s = opt_str("SAMD_ONCHIP_WAVES");
-    const char* e = e_s.c_str();
-    const int v = atoi(e);
-    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) h->v2.dec_waves = v;      // experiments: force a workgroup size
-  }
   const int nw = h->v2.dec_waves;
   lpt_schedule(ci, nw, &cp, &cl);
   lpt_schedule(vi, nw, &vp, &vl);

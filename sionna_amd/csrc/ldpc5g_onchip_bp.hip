@@ -182,241 +182,257 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_bp_kernel(
 
 static const int kBpCnDegrees[] = {3, 4, 5, 6, 7, 8, 9, 10, 19};
 
-int build_onchip_bp_tables(samd_ldpc5g* h, const BaseRows& by_row) {
-  const int z = h->z;
-  const int ncu = (h->n_cn + z - 1) / z, nbu = (h->n_vn + z - 1) / z;
-  h->bp.ok = 0;
-  if (h->mb > 255 || h->nb > 255 || (z + 63) / 64 > 255) return SAMD_OK;
-  std::vector<int32_t> row_off(h->mb, 0), col_ent((size_t)h->nb * kColStride, 0), col_deg(h->nb, 0);
+// ---- cost model of the explicit-message schedule, stated once.  Costs are ~ instructions; lpt_schedule balances their
+// sum per wave.
+// Fixed cost per CN / VN item: measured at C2 in round 2, a fixed cost of ~20 edges per item balances best.
+constexpr int kMsCnOvh = 400, kMsVnOvh = 200;
+// Cost per edge of a CN pair item (a single-chunk item: half).  Round 3, item trace of the grouped kernel
+// (tools/ms_itrace.py, profiles/r03b/ms_itrace_r03d.txt): a CN pair item takes 127 d + 1790 cycles, a VN pair item
+// 115 d + 2240, a single-chunk VN item 111 d + 1040 - one chunk has one dependency chain, so its edges cost what a pair's
+// edge PAIRS cost.  18: the model of round 2; 36 for the codes of the grouped kernel: +1.7 % at C2
+// (profiles/r03b/ms_cost_r03f.txt) - the other lifting sizes lose 2-3 % with it (profiles/r03b/ldpc_sweep_r03_s36.json
+// vs ..._s18.json)
+constexpr int kMsCnSlope = 18, kMsCnSlopeGrouped = 36;
+// Granularity: C2 has 29 variable-node items for 16 waves - the four single-chunk items of the degree-30 / 28 columns
+// are a wave's whole phase and leave it under-loaded, the other waves carry two pair items.  A pair item of the busiest
+// wave is cut into its two single-chunk items (a little more work in total: one dependency chain each) as long as
+// that shortens the longest wave under the LPT rule, at most kMsVnRefineTries times: +0.5 % at C2,
+// profiles/r03b/ms_refine_r03z.txt.  A half costs half the pair + kMsVnRefineCost (item trace: V12 pair 3.6 k cycles, a
+// single-chunk item of that degree ~2.4 k).
+// Lifting sizes of two chunks only (Z = 128: +1.3 % at C2, +1.1 % at k=2816 n=5632; codes of three or four chunks have
+// enough items per wave and lose 5 % - ms_refine_codes_r03z.txt).
+constexpr int kMsVnRefineTries = 8, kMsVnRefineCost = 70;
+// The same for the check-node pair items (the grouped kernel has the single-chunk bodies under key + 64): C2 +2 %,
+// profiles/r03b/ms_refine_cn3_r03z.txt; rows of degree 5 / 6 with a fused column only - every further single-chunk body
+// in the kernel slows the items that do not use it: all 17 bodies -2 %, four -1.4 %, two -0.3 %
+constexpr int kMsCnRefineTries = 4, kMsCnRefineCost = 150;
 
+typedef std::vector<std::pair<int, int32_t>> MsItems;            // (cost, id) as lpt_schedule takes them
+
+// What the steps of build_onchip_bp_tables hand on, in the order they fill it
+struct MsBuild {
+  int z = 0, ncu = 0, nbu = 0, chunks = 0;
+  // 1. message layout (both engines)
   int edges = 0;
-  for (int r = 0; r < ncu; ++r) {
+  std::vector<int32_t> row_off, col_ent, col_deg;
+  // 2. compact column tables, fused columns, packed tails
+  std::vector<int32_t> col_ent2, col_start;
+  std::vector<int> fused_col;                                 // per row: its fused degree-1 column or -1
+  std::vector<char> col_fused;
+  int groups = 1, tail_sh = 6;                                // rows per packed-tail item, log2 of its lane-group width
+  std::vector<std::vector<int>> packed, vpacked;              // rows / columns of every packed-tail item
+  std::vector<int> packed_key, vpacked_deg;                   // degree | fused << 5 / column degree of the item
+  // 3. items and their per-wave lists (VN: per-iteration lists, then the fused columns)
+  MsItems ci2, vi2;
+  std::vector<int32_t> mcp, mcl, mvp, mvl;
+  std::vector<int> cprio, vprio;
+};
+
+// 1. Message layout: one block of Z floats per edge, row-major; waves per workgroup from the LDS footprint.  False: the
+// code is left to the other engines.
+static bool bp_message_layout(samd_ldpc5g* h, const BaseRows& by_row, MsBuild& b) {
+  const int z = b.z;
+  b.row_off.assign(h->mb, 0); b.col_ent.assign((size_t)h->nb * kColStride, 0); b.col_deg.assign(h->nb, 0);
+  int edges = 0;
+  for (int r = 0; r < b.ncu; ++r) {
     const int d = (int)by_row[r].size();
-    if (std::find(std::begin(kBpCnDegrees), std::end(kBpCnDegrees), d) == std::end(kBpCnDegrees)) return SAMD_OK;
-    row_off[r] = (edges * z * 4) | (d << 18);               // byte offset of the first edge block | degree << 18
+    if (std::find(std::begin(kBpCnDegrees), std::end(kBpCnDegrees), d) == std::end(kBpCnDegrees)) return false;
+    b.row_off[r] = (edges * z * 4) | (d << 18);             // byte offset of the first edge block | degree << 18
     for (int i = 0; i < d; ++i) {
       const int c = by_row[r][i].first, s = by_row[r][i].second;
-      if (c >= nbu || col_deg[c] >= kColStride) return SAMD_OK;
-      col_ent[(size_t)c * kColStride + col_deg[c]++] = ((edges + i) * z * 4) | ((s * 4) << 18);   // rows ascending
+      if (c >= b.nbu || b.col_deg[c] >= kColStride) return false;
+      b.col_ent[(size_t)c * kColStride + b.col_deg[c]++] = ((edges + i) * z * 4) | ((s * 4) << 18);   // rows ascending
     }
     edges += d;
   }
   const size_t msg_bytes = (size_t)edges * z * 4;
-  if (msg_bytes > 160 * 1024 || msg_bytes >= (1u << 18)) return SAMD_OK;   // the HBM-resident engine takes it
-  h->bp.edges = edges;
-  size_t lds = msg_bytes + (size_t)nbu * z * 4;
+  if (msg_bytes > 160 * 1024 || msg_bytes >= (1u << 18)) return false;   // the HBM-resident engine takes it
+  b.edges = h->bp.edges = edges;
+  size_t lds = msg_bytes + (size_t)b.nbu * z * 4;
   h->bp.llr_global = 0;
   if (lds > 160 * 1024) { h->bp.llr_global = 1; lds = msg_bytes; }
   h->bp.waves = 16;
   if (!h->bp.llr_global)
     for (int nwc : {8, 4, 2, 1})
       if (lds * (size_t)(kDecWaves / nwc) <= 160 * 1024) h->bp.waves = nwc;
-  if (opt_set("SAMD_ONCHIP_BP_WAVES")) {
-    const std::string e_s = opt_str("SAMD_ONCHIP_BP_WAVES");
-    const char* e = e_s.c_str();
-    const int v = atoi(e);
-    if (!h->bp.llr_global && (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && lds * (size_t)(kDecWaves / v) <= 160 * 1024)
-      h->bp.waves = v;
-  }
+  return true;
+}
+
+// The first boxplus kernel's own lists: one item per (row, chunk) / (column, chunk)
+static void bp_item_lists(const samd_ldpc5g* h, const BaseRows& by_row, const MsBuild& b, std::vector<int32_t>& cp,
+                          std::vector<int32_t>& cl, std::vector<int32_t>& vp, std::vector<int32_t>& vl) {
   // items: CN cost ~ degree (two phi evaluations per edge), VN cost ~ degree
-  const int chunks = (z + 63) / 64;
-  std::vector<std::pair<int, int32_t>> ci, vi;
-  for (int r = 0; r < ncu; ++r)
-    for (int q = 0; q < chunks; ++q)
+  MsItems ci, vi;
+  for (int r = 0; r < b.ncu; ++r)
+    for (int q = 0; q < b.chunks; ++q)
       ci.push_back({8 * (int)by_row[r].size(), r | (q << 8)});   // also chunks of pruned check nodes only: the item keeps their slots at 0
-  for (int c = 0; c < nbu; ++c)
-    for (int q = 0; q < chunks; ++q)
-      if (c * z + q * 64 < h->n_vn) vi.push_back({col_deg[c] + 2, c | (q << 8)});
-  std::vector<int32_t> cp, cl, vp, vl;
+  for (int c = 0; c < b.nbu; ++c)
+    for (int q = 0; q < b.chunks; ++q)
+      if (c * b.z + q * 64 < h->n_vn) vi.push_back({b.col_deg[c] + 2, c | (q << 8)});
   lpt_schedule(ci, h->bp.waves, &cp, &cl);
   lpt_schedule(vi, h->bp.waves, &vp, &vl);
-  {
-    const std::vector<int> pc = item_priorities(ci, cp, cl), pv = item_priorities(vi, vp, vl);   // see ldpc5g.h
-    for (size_t j = 0; j < cl.size(); ++j) cl[j] |= pc[j] << 24;
-    for (size_t j = 0; j < vl.size(); ++j) vl[j] |= pv[j] << 24;
-  }
-  // ldpc5g_onchip_ms.hip: compact per-column edge tables (block byte offset, 4 shift) - a few KB, they stay in the
-  // scalar cache - and self-contained two-dword list entries in the same order as the lists above
-  std::vector<int32_t> col_ent2, col_start(h->nb, 0), cl2, vl2;
+  const std::vector<int> pc = item_priorities(ci, cp, cl), pv = item_priorities(vi, vp, vl);   // see ldpc5g.h
+  for (size_t j = 0; j < cl.size(); ++j) cl[j] |= pc[j] << 24;
+  for (size_t j = 0; j < vl.size(); ++j) vl[j] |= pv[j] << 24;
+}
+
+// 2. ldpc5g_onchip_ms.hip: compact per-column edge tables, the fused degree-1 columns and the packed tails
+static void ms_fused_and_tails(const samd_ldpc5g* h, const BaseRows& by_row, MsBuild& b) {
+  const int z = b.z, ncu = b.ncu, nbu = b.nbu, chunks = b.chunks;
+  // compact per-column edge tables (block byte offset, 4 shift) - a few KB, they stay in the scalar cache
+  b.col_start.assign(h->nb, 0);
   for (int c = 0; c < h->nb; ++c) {
-    col_start[c] = (int32_t)col_ent2.size();
-    for (int i = 0; i < col_deg[c]; ++i) {
-      const int32_t e = col_ent[(size_t)c * kColStride + i];
-      col_ent2.push_back(e & 0x3FFFF);
-      col_ent2.push_back((int32_t)((uint32_t)e >> 18));
+    b.col_start[c] = (int32_t)b.col_ent2.size();
+    for (int i = 0; i < b.col_deg[c]; ++i) {
+      const int32_t e = b.col_ent[(size_t)c * kColStride + i];
+      b.col_ent2.push_back(e & 0x3FFFF);
+      b.col_ent2.push_back((int32_t)((uint32_t)e >> 18));
     }
   }
-  col_ent2.resize(col_ent2.size() + 64, 0);                    // wide scalar loads may run past the last edge
+  b.col_ent2.resize(b.col_ent2.size() + 64, 0);                // wide scalar loads may run past the last edge
   // rows whose last edge is the only edge of its column with shift 0 (extension part of the base graph): that
   // degree-1 VN is updated inside the CN phase (ms_cn_row<D, true>) and leaves the per-iteration VN lists
-  std::vector<int> fused_col(h->mb, -1);
-  std::vector<char> col_fused(h->nb, 0);
+  b.fused_col.assign(h->mb, -1);
+  b.col_fused.assign(h->nb, 0);
   for (int r = 0; r < ncu; ++r) {
     const int d = (int)by_row[r].size();
     const int c = by_row[r][d - 1].first, sft = by_row[r][d - 1].second;
-    if (col_deg[c] == 1 && sft == 0 && d >= 3 && d <= 10) { fused_col[r] = c; col_fused[c] = 1; }
+    if (b.col_deg[c] == 1 && sft == 0 && d >= 3 && d <= 10) { b.fused_col[r] = c; b.col_fused[c] = 1; }
   }
-  // two consecutive fully valid chunks of a row / column (degree <= 12) form one pair item (bit 24);
-  // weights ~ instructions: 9 (CN) / 5 (VN) per edge and chunk + ~40 for the item's dispatch
-  std::vector<std::pair<int, int32_t>> ci2, vi2, vf2;
-  // development knobs: per-item overhead of the cost model, capacities by wave launch order
-  // (measured at C2 with tools/ms_sweep.py: a fixed cost of ~20 edges per item balances best)
-  const int cn_ovh = (int)opt_int("SAMD_MS_CN_OVH", 400);
-  const int vn_ovh = (int)opt_int("SAMD_MS_VN_OVH", 200);
-  // cost per edge of a pair item / of a single-chunk item, and the fixed cost of a single-chunk VN item.  Round 3, item
-  // trace of the grouped kernel (tools/ms_itrace.py, profiles/r03b/ms_itrace_r03d.txt): a CN pair item takes
-  // 127 d + 1790 cycles, a VN pair item 115 d + 2240, a single-chunk VN item 111 d + 1040 - one chunk has one dependency
-  // chain, so its edges cost what a pair's edge PAIRS cost.
-  // 18: r02 model; 36 for the codes of the grouped kernel: +1.7 % at C2 (profiles/r03b/ms_cost_r03f.txt) - the other
-  // lifting sizes lose 2-3 % with it (profiles/r03b/ldpc_sweep_r03_s36.json vs ..._s18.json)
-  const bool grouped_code = z % 128 == 0 && h->n_cn % z == 0 && h->n_vn % z == 0;
-  const int cn_slope = (int)opt_int("SAMD_MS_CN_SLOPE", (grouped_code ? 36 : 18));
-  const int vn_single = (int)opt_int("SAMD_MS_VN_SINGLE", 0);   // 1: 10 d + vn_ovh / 2
   // Z not a multiple of 64: the last chunk of a row has `tail` < 64 lifted copies.  With tail <= 32 the tails of
   // 64 / gw rows of the same degree (and fused flag) are packed into one item (lane group g works for row g) - at
   // Z = 80 the 16-lane tails of four rows share a pass instead of running at 25 % lane utilisation each
   const int tail = z - 64 * (chunks - 1);
   int gw = 64;
   while (gw / 2 >= tail && gw > 8) gw /= 2;
-  if (opt_set("SAMD_MS_NOPACK")) gw = 64;
-  const int groups = 64 / gw;
-  int tail_sh = 0;
-  while ((1 << tail_sh) < gw) ++tail_sh;
-  std::vector<std::vector<int>> packed;                       // rows of every packed-tail item
-  std::vector<int> packed_key;                                // degree | fused << 5 of the item
+  const int groups = b.groups = 64 / gw;
+  b.tail_sh = 0;
+  while ((1 << b.tail_sh) < gw) ++b.tail_sh;
   {
     std::vector<std::vector<int>> bucket(64);
     if (groups >= 2)
-      for (int r = 0; r < ncu; ++r) bucket[(int)by_row[r].size() | ((fused_col[r] >= 0) << 5)].push_back(r);
+      for (int r = 0; r < ncu; ++r) bucket[(int)by_row[r].size() | ((b.fused_col[r] >= 0) << 5)].push_back(r);
     for (int key = 0; key < 64; ++key)
       for (size_t i = 0; i < bucket[key].size(); i += groups) {
-        packed.emplace_back(bucket[key].begin() + i, bucket[key].begin() + std::min(bucket[key].size(), i + groups));
-        packed_key.push_back(key);
+        b.packed.emplace_back(bucket[key].begin() + i, bucket[key].begin() + std::min(bucket[key].size(), i + groups));
+        b.packed_key.push_back(key);
       }
   }
+  // the same packing for the tails of the (not fused) columns, by column degree
+  {
+    std::vector<std::vector<int>> bucket(64);
+    if (groups >= 2)
+      for (int c = 0; c < nbu; ++c)
+        if (!b.col_fused[c] && c * z + (chunks - 1) * 64 < h->n_vn && b.col_deg[c] >= 1 && b.col_deg[c] <= 30)
+          bucket[b.col_deg[c]].push_back(c);
+    for (int dg = 0; dg < 64; ++dg)
+      for (size_t i = 0; i < bucket[dg].size(); i += groups) {
+        b.vpacked.emplace_back(bucket[dg].begin() + i, bucket[dg].begin() + std::min(bucket[dg].size(), i + groups));
+        b.vpacked_deg.push_back(dg);
+      }
+  }
+}
+
+// Cuts pair items of the busiest wave into their two single-chunk items while that shortens the longest wave under the LPT
+// rule (see kMsVnRefineTries): a half costs half the pair + extra; may_cut(row or column) says which pairs may be cut.
+template <typename MayCut>
+static void ms_refine(MsItems& items, int nw, int tries, int extra, MayCut&& may_cut) {
+  auto makespan = [&](const MsItems& its, std::vector<int>* owner) {
+    std::vector<size_t> order(its.size());
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return its[a].first > its[b].first; });
+    std::vector<double> load(nw, 0.0);
+    if (owner) owner->assign(its.size(), 0);
+    for (size_t i : order) {
+      int w = 0;
+      for (int q = 1; q < nw; ++q)
+        if (load[q] + its[i].first + 3 < load[w] + its[i].first + 3) w = q;
+      load[w] += its[i].first + 3;
+      if (owner) (*owner)[i] = w;
+    }
+    int mw = 0;
+    for (int q = 1; q < nw; ++q) if (load[q] > load[mw]) mw = q;
+    return std::make_pair(load[mw], mw);
+  };
+  for (int t = 0; t < tries; ++t) {
+    std::vector<int> owner;
+    const auto base = makespan(items, &owner);
+    int best = -1;
+    double best_m = base.first;
+    for (size_t i = 0; i < items.size(); ++i) {
+      if (owner[i] != base.second || !((items[i].second >> 24) & 1) || !may_cut(items[i].second & 0xFF)) continue;
+      auto trial = items;
+      const int c = trial[i].second & 0xFF, q = (trial[i].second >> 8) & 0xFF, half = trial[i].first / 2 + extra;
+      trial[i] = {half, c | (q << 8)};
+      trial.push_back({half, c | ((q + 1) << 8)});
+      const double m = makespan(trial, nullptr).first;
+      if (m < best_m) { best_m = m; best = (int)i; }
+    }
+    if (best < 0) break;
+    const int c = items[best].second & 0xFF, q = (items[best].second >> 8) & 0xFF, half = items[best].first / 2 + extra;
+    items[best] = {half, c | (q << 8)};
+    items.push_back({half, c | ((q + 1) << 8)});
+  }
+}
+
+// 3. Items and their lists.  Two consecutive fully valid chunks of a row / column (degree <= 12) form one pair item
+// (bit 24), a packed tail is one item (bit 25); weights ~ instructions: 9 (CN) / 5 (VN) per edge and chunk + the item's
+// dispatch (kMsCnOvh / kMsVnOvh).
+static void ms_item_lists(const samd_ldpc5g* h, const BaseRows& by_row, MsBuild& b) {
+  const int z = b.z, ncu = b.ncu, nbu = b.nbu, chunks = b.chunks, groups = b.groups, nw = h->bp.waves;
+  const std::vector<int>& fused_col = b.fused_col;
+  const bool grouped_code = z % 128 == 0 && h->n_cn % z == 0 && h->n_vn % z == 0;
+  const int cn_slope = grouped_code ? kMsCnSlopeGrouped : kMsCnSlope;
+  MsItems& ci2 = b.ci2;
+  MsItems& vi2 = b.vi2;
+  MsItems vf2;                                                // fused columns: v2c of iteration 0 only
   for (int r = 0; r < ncu; ++r)
     for (int q = 0; q < chunks; ++q) {
       const int d = (int)by_row[r].size();                    // chunks of pruned check nodes only still get an item (it zeroes their slots)
       if (groups >= 2 && q == chunks - 1) continue;           // the tail goes into a packed item
       const bool pair = (q + 2) * 64 <= z && r * z + (q + 2) * 64 <= h->n_cn &&
                         (fused_col[r] < 0 || fused_col[r] * z + (q + 2) * 64 <= h->n_vn);
-      if (pair) { ci2.push_back({cn_slope * d + cn_ovh, r | (q << 8) | (1 << 24)}); ++q; }
-      else ci2.push_back({cn_slope / 2 * d + cn_ovh, r | (q << 8)});
+      if (pair) { ci2.push_back({cn_slope * d + kMsCnOvh, r | (q << 8) | (1 << 24)}); ++q; }
+      else ci2.push_back({cn_slope / 2 * d + kMsCnOvh, r | (q << 8)});
     }
-  for (size_t i = 0; i < packed.size(); ++i)
-    ci2.push_back({9 * (packed_key[i] & 31) + cn_ovh, (int32_t)i | (1 << 25)});
-  // the same packing for the tails of the (not fused) columns, by column degree
-  std::vector<std::vector<int>> vpacked;
-  std::vector<int> vpacked_deg;
-  {
-    std::vector<std::vector<int>> bucket(64);
-    if (groups >= 2)
-      for (int c = 0; c < nbu; ++c)
-        if (!col_fused[c] && c * z + (chunks - 1) * 64 < h->n_vn && col_deg[c] >= 1 && col_deg[c] <= 30)
-          bucket[col_deg[c]].push_back(c);
-    for (int dg = 0; dg < 64; ++dg)
-      for (size_t i = 0; i < bucket[dg].size(); i += groups) {
-        vpacked.emplace_back(bucket[dg].begin() + i, bucket[dg].begin() + std::min(bucket[dg].size(), i + groups));
-        vpacked_deg.push_back(dg);
-      }
-  }
+  for (size_t i = 0; i < b.packed.size(); ++i)
+    ci2.push_back({9 * (b.packed_key[i] & 31) + kMsCnOvh, (int32_t)i | (1 << 25)});
   for (int c = 0; c < nbu; ++c)
     for (int q = 0; q < chunks; ++q) {
       if (c * z + q * 64 >= h->n_vn) continue;
-      if (groups >= 2 && q == chunks - 1 && !col_fused[c] && col_deg[c] >= 1 && col_deg[c] <= 30) continue;   // packed below
-      const bool pair = col_deg[c] <= 12 && (q + 2) * 64 <= z && c * z + (q + 2) * 64 <= h->n_vn;
-      auto& dst = col_fused[c] ? vf2 : vi2;
-      if (pair) { dst.push_back({10 * col_deg[c] + vn_ovh, c | (q << 8) | (1 << 24)}); ++q; }
-      else if (vn_single) dst.push_back({10 * col_deg[c] + vn_ovh / 2, c | (q << 8)});
-      else dst.push_back({5 * col_deg[c] + vn_ovh, c | (q << 8)});
+      if (groups >= 2 && q == chunks - 1 && !b.col_fused[c] && b.col_deg[c] >= 1 && b.col_deg[c] <= 30) continue;   // packed below
+      const bool pair = b.col_deg[c] <= 12 && (q + 2) * 64 <= z && c * z + (q + 2) * 64 <= h->n_vn;
+      auto& dst = b.col_fused[c] ? vf2 : vi2;
+      if (pair) { dst.push_back({10 * b.col_deg[c] + kMsVnOvh, c | (q << 8) | (1 << 24)}); ++q; }
+      else dst.push_back({5 * b.col_deg[c] + kMsVnOvh, c | (q << 8)});
     }
-  for (size_t i = 0; i < vpacked.size(); ++i) vi2.push_back({5 * vpacked_deg[i] + vn_ovh, (int32_t)i | (1 << 25)});
-  std::vector<int32_t> mcp, mcl, mvp, mvl, mfp, mfl;
-  // wave w runs on SIMD w % 4 as its (w / 4)-th oldest wave: optional capacities by age class (SAMD_MS_CAP="a,b,c,d")
-  std::vector<double> cap(h->bp.waves, 1.0);
-  {
-    double cls[4] = {1.0, 1.0, 1.0, 1.0};
-    if (opt_set("SAMD_MS_CAP")) sscanf(opt_str("SAMD_MS_CAP").c_str(), "%lf,%lf,%lf,%lf", &cls[0], &cls[1], &cls[2], &cls[3]);
-    const int per_simd = std::max(1, h->bp.waves / 4);
-    for (int wv = 0; wv < h->bp.waves; ++wv) cap[wv] = cls[std::min(3, (wv / 4) * 4 / per_simd)];
-  }
-  // Granularity: C2 has 29 variable-node items for 16 waves - the four single-chunk items of the degree-30 / 28 columns
-  // are a wave's whole phase and leave it under-loaded, the other waves carry two pair items.  A pair item of the busiest
-  // wave is cut into its two single-chunk items (a little more work in total: one dependency chain each) as long as
-  // that shortens the longest wave under the LPT rule (SAMD_MS_VN_REFINE = number of cuts tried, 0 = off): +0.5 % at C2,
-  // profiles/r03b/ms_refine_r03z.txt.  A half costs half the pair + `extra` (item trace: V12 pair 3.6 k cycles, a
-  // single-chunk item of that degree ~2.4 k).
-  // Lifting sizes of two chunks only (Z = 128: +1.3 % at C2, +1.1 % at k=2816 n=5632; codes of three or four chunks have
-  // enough items per wave and lose 5 % - ms_refine_codes_r03z.txt).
-  // development (tools/ms_autotune.py): item costs perturbed by +-SAMD_MS_PERTURB_PCT % from a seeded generator - a
-  // search over LPT assignments near the model's by measurement
-#ifdef SAMD_DEV                                               // changes the schedule search, not for product builds
-  if (opt_set("SAMD_MS_PERTURB")) {
-    unsigned long long st = 0x9E3779B97F4A7C15ull * (unsigned long long)(opt_int("SAMD_MS_PERTURB", 0) + 1);
-    const int pct = (int)opt_int("SAMD_MS_PERTURB_PCT", 8);
-    auto rnd = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return (double)(st >> 11) / 9007199254740992.0; };
-    for (auto* items : {&ci2, &vi2})
-      for (auto& it : *items) it.first = std::max(1, (int)std::lround(it.first * (1.0 + pct / 100.0 * (2.0 * rnd() - 1.0))));
-  }
-#endif
-  auto refine = [&](std::vector<std::pair<int, int32_t>>& items, int tries, int extra, auto&& may_cut) {
-    auto makespan = [&](const std::vector<std::pair<int, int32_t>>& its, std::vector<int>* owner) {
-      std::vector<size_t> order(its.size());
-      std::iota(order.begin(), order.end(), 0);
-      std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return its[a].first > its[b].first; });
-      std::vector<double> load(h->bp.waves, 0.0);
-      if (owner) owner->assign(its.size(), 0);
-      for (size_t i : order) {
-        int w = 0;
-        for (int q = 1; q < h->bp.waves; ++q)
-          if ((load[q] + its[i].first + 3) / cap[q] < (load[w] + its[i].first + 3) / cap[w]) w = q;
-        load[w] += its[i].first + 3;
-        if (owner) (*owner)[i] = w;
-      }
-      int mw = 0;
-      for (int q = 1; q < h->bp.waves; ++q) if (load[q] > load[mw]) mw = q;
-      return std::make_pair(load[mw], mw);
-    };
-    for (int t = 0; t < tries; ++t) {
-      std::vector<int> owner;
-      const auto base = makespan(items, &owner);
-      int best = -1;
-      double best_m = base.first;
-      for (size_t i = 0; i < items.size(); ++i) {
-        if (owner[i] != base.second || !((items[i].second >> 24) & 1) || !may_cut(items[i].second & 0xFF)) continue;
-        auto trial = items;
-        const int c = trial[i].second & 0xFF, q = (trial[i].second >> 8) & 0xFF, half = trial[i].first / 2 + extra;
-        trial[i] = {half, c | (q << 8)};
-        trial.push_back({half, c | ((q + 1) << 8)});
-        const double m = makespan(trial, nullptr).first;
-        if (m < best_m) { best_m = m; best = (int)i; }
-      }
-      if (best < 0) break;
-      const int c = items[best].second & 0xFF, q = (items[best].second >> 8) & 0xFF, half = items[best].first / 2 + extra;
-      items[best] = {half, c | (q << 8)};
-      items.push_back({half, c | ((q + 1) << 8)});
-    }
-  };
-  refine(vi2, (int)opt_int("SAMD_MS_VN_REFINE", (chunks == 2 ? 8 : 0)),
-         (int)opt_int("SAMD_MS_VN_REFINE_COST", 70), [](int) { return true; });
-  // the same for the check-node pair items (the grouped kernel has the single-chunk bodies under key + 64)
-  // (C2: +2 %, profiles/r03b/ms_refine_cn3_r03z.txt; rows of degree 5 / 6 with a fused column only - every further
-  // single-chunk body in the kernel slows the items that do not use it: all 17 bodies -2 %, four -1.4 %, two -0.3 %)
-  refine(ci2, (int)opt_int("SAMD_MS_CN_REFINE", (chunks == 2 ? 4 : 0)),
-         (int)opt_int("SAMD_MS_CN_REFINE_COST", 150),
-         [&](int r) { const int d = (int)by_row[r].size(); return fused_col[r] >= 0 && d >= 5 && d <= 6; });
-  lpt_schedule(ci2, h->bp.waves, &mcp, &mcl, &cap);
-  lpt_schedule(vi2, h->bp.waves, &mvp, &mvl, &cap);
-  const std::vector<int> cprio = item_priorities(ci2, mcp, mcl), vprio = item_priorities(vi2, mvp, mvl);
-  lpt_schedule(vf2, h->bp.waves, &mfp, &mfl);
-  for (int32_t o : mfp) mvp.push_back(o + (int32_t)mvl.size());
-  mvl.insert(mvl.end(), mfl.begin(), mfl.end());
-  std::vector<int32_t> tail_tab;
-  for (size_t i = 0; i < packed.size(); ++i)
+  for (size_t i = 0; i < b.vpacked.size(); ++i) vi2.push_back({5 * b.vpacked_deg[i] + kMsVnOvh, (int32_t)i | (1 << 25)});
+  ms_refine(vi2, nw, chunks == 2 ? kMsVnRefineTries : 0, kMsVnRefineCost, [](int) { return true; });
+  ms_refine(ci2, nw, chunks == 2 ? kMsCnRefineTries : 0, kMsCnRefineCost,
+            [&](int r) { const int d = (int)by_row[r].size(); return fused_col[r] >= 0 && d >= 5 && d <= 6; });
+  std::vector<int32_t> mfp, mfl;
+  lpt_schedule(ci2, nw, &b.mcp, &b.mcl);
+  lpt_schedule(vi2, nw, &b.mvp, &b.mvl);
+  b.cprio = item_priorities(ci2, b.mcp, b.mcl);
+  b.vprio = item_priorities(vi2, b.mvp, b.mvl);
+  lpt_schedule(vf2, nw, &mfp, &mfl);
+  for (int32_t o : mfp) b.mvp.push_back(o + (int32_t)b.mvl.size());
+  b.mvl.insert(b.mvl.end(), mfl.begin(), mfl.end());
+}
+
+// 4. The lists as the list-walking kernel reads them: self-contained two-dword entries in the order of step 3, and the
+// tables of the packed tails
+static void ms_encode_lists(const BaseRows& by_row, const MsBuild& b, std::vector<int32_t>& cl2, std::vector<int32_t>& vl2,
+                            std::vector<int32_t>& tail_tab, std::vector<int32_t>& vtail_tab) {
+  const int chunks = b.chunks, groups = b.groups;
+  const std::vector<int>& fused_col = b.fused_col;
+  const std::vector<int>& cprio = b.cprio;
+  const std::vector<int>& vprio = b.vprio;
+  for (size_t i = 0; i < b.packed.size(); ++i)
     for (int g = 0; g < groups; ++g) {
-      if (g < (int)packed[i].size()) {
-        const int r = packed[i][g];
-        tail_tab.push_back(row_off[r] & 0x3FFFF);
+      if (g < (int)b.packed[i].size()) {
+        const int r = b.packed[i][g];
+        tail_tab.push_back(b.row_off[r] & 0x3FFFF);
         tail_tab.push_back(r | ((fused_col[r] >= 0 ? fused_col[r] : 0) << 16));
       } else {
         tail_tab.push_back(0);
@@ -424,170 +440,194 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const BaseRows& by_row) {
       }
     }
   tail_tab.resize(tail_tab.size() + 2, 0);
-  h->ms.tail_sh = tail_sh;
-  for (size_t j = 0; j < mcl.size(); ++j) {
-    const int32_t d = mcl[j];
+  for (size_t j = 0; j < b.mcl.size(); ++j) {
+    const int32_t d = b.mcl[j];
     if ((d >> 25) & 1) {                                      // packed tails: table base | key, last chunk | flag
       const int i = d & 0xFFFF;
-      cl2.push_back((int32_t)(i * groups) | (packed_key[i] << 18));
+      cl2.push_back((int32_t)(i * groups) | (b.packed_key[i] << 18));
       cl2.push_back(((chunks - 1) << 8) | (1 << 26) | (cprio[j] << 24));
       continue;
     }
     const int r = d & 0xFF, f = fused_col[r] >= 0, pr = (d >> 24) & 1;
-    cl2.push_back((row_off[r] & 0x3FFFF) | (((int)by_row[r].size() | (f << 5) | (pr << 6)) << 18));
+    cl2.push_back((b.row_off[r] & 0x3FFFF) | (((int)by_row[r].size() | (f << 5) | (pr << 6)) << 18));
     cl2.push_back((d & 0xFFFF) | ((f ? fused_col[r] : 0) << 16) | (cprio[j] << 24));
   }
-  std::vector<int32_t> vtail_tab;
-  for (size_t i = 0; i < vpacked.size(); ++i)
+  for (size_t i = 0; i < b.vpacked.size(); ++i)
     for (int g = 0; g < groups; ++g) {
-      const bool has = g < (int)vpacked[i].size();
-      vtail_tab.push_back(has ? col_start[vpacked[i][g]] : 0);
-      vtail_tab.push_back(has ? vpacked[i][g] : 0xFF);
+      const bool has = g < (int)b.vpacked[i].size();
+      vtail_tab.push_back(has ? b.col_start[b.vpacked[i][g]] : 0);
+      vtail_tab.push_back(has ? b.vpacked[i][g] : 0xFF);
     }
   vtail_tab.resize(vtail_tab.size() + 2, 0);
-  for (size_t j = 0; j < mvl.size(); ++j) {
-    const int32_t d = mvl[j];
+  for (size_t j = 0; j < b.mvl.size(); ++j) {
+    const int32_t d = b.mvl[j];
     if ((d >> 25) & 1) {                                      // packed tails: last chunk | degree | flag, table base
       const int i = d & 0xFFFF;
-      vl2.push_back(((chunks - 1) << 8) | (vpacked_deg[i] << 16) | (1 << 22) | ((j < vprio.size() ? vprio[j] : 0) << 24));
+      vl2.push_back(((chunks - 1) << 8) | (b.vpacked_deg[i] << 16) | (1 << 22) | ((j < vprio.size() ? vprio[j] : 0) << 24));
       vl2.push_back(i * groups);
       continue;
     }
     const int c = d & 0xFF, pr = (d >> 24) & 1;
-    vl2.push_back((d & 0xFFFF) | ((col_deg[c] | (pr << 5)) << 16) | ((j < vprio.size() ? vprio[j] : 0) << 24));
-    vl2.push_back(col_start[c]);
+    vl2.push_back((d & 0xFFFF) | ((b.col_deg[c] | (pr << 5)) << 16) | ((j < vprio.size() ? vprio[j] : 0) << 24));
+    vl2.push_back(b.col_start[c]);
   }
   cl2.resize(cl2.size() + 2, 0); vl2.resize(vl2.size() + 2, 0);
-  // ---- grouped dispatch (ldpc5g_decode_msg_kernel): the items of every wave sorted by body type.  Only for codes whose
-  // items are all full chunk pairs (Z a multiple of 128, no partially pruned base row) on 16 waves.
+}
+
+// 5. Grouped dispatch (ldpc5g_decode_msg_kernel): the items of every wave sorted by body type, and the same schedule as
+// data for the source generator of the specialised kernel (JitPlan, ldpc5g_jit.cpp).  Only for codes whose items are all
+// full chunk pairs (Z a multiple of 128, no partially pruned base row) on 16 waves; the caller has checked that.
+// Returns g_ok and, with it, the plan (else null).
+static int ms_grouped_dispatch(const samd_ldpc5g* h, const BaseRows& by_row, const MsBuild& b, std::vector<int32_t>& g_ptr,
+                               std::vector<int32_t>& g_cn, std::vector<int32_t>& g_vn, std::vector<int32_t>& i_cn,
+                               std::vector<int32_t>& i_vn, JitPlan** plan_out) {
+  const int z = b.z, ncu = b.ncu, nbu = b.nbu;
+  const std::vector<int>& fused_col = b.fused_col;
+  bool ok = true;
+  struct It { int cost, key; int32_t x, y; int idx, pr, q; };
+  JitPlan* plan = new JitPlan();
+  plan->cn.resize(h->bp.waves); plan->vn.resize(h->bp.waves);
+  auto cost_in = [](const MsItems& items, int32_t id) {
+    for (auto& it : items)
+      if (it.second == id) return it.first;
+    return 0;
+  };
+  const int nwv = h->bp.waves;
+  for (int phase = 0; phase < 2 && ok; ++phase) {
+    const std::vector<int32_t>& lp = phase ? b.mvp : b.mcp;
+    const std::vector<int32_t>& ll = phase ? b.mvl : b.mcl;
+    std::vector<std::vector<It>> per(nwv);
+    double longest = 1.0;
+    for (int wv = 0; wv < nwv; ++wv) {
+      double tot = 0.0;
+      for (int j = lp[wv]; j < lp[wv + 1]; ++j) {
+        const int32_t d = ll[j];
+        if ((d >> 25) & 1) { ok = false; break; }
+        const int idx = d & 0xFF, q = (d >> 8) & 0xFF, pr = (d >> 24) & 1;
+        It it;
+        it.idx = idx; it.pr = pr; it.q = q;
+        it.cost = cost_in(phase ? b.vi2 : b.ci2, d) + 3;
+        if (!phase) {
+          const int f = fused_col[idx] >= 0;
+          it.key = (int)by_row[idx].size() | (f << 5) | (pr ? 0 : 64);      // (64: a single chunk of the row)
+          it.x = (b.row_off[idx] & 0x3FFFF) + 256 * q;
+          it.y = f ? fused_col[idx] * z + q * 64 : 0;
+        } else {
+          it.key = b.col_deg[idx] | (pr << 5);
+          it.x = (idx * z + q * 64) | (pr << 23);
+          it.y = b.col_start[idx] | (q << 20);
+          if (b.col_start[idx] >= (1 << 20) || idx * z + q * 64 >= (1 << 23)) ok = false;
+        }
+        // every key must have a compiled body in ldpc5g_decode_msg_kernel (its switches end in `default: break`, which
+        // would skip the item silently): CN degrees 3..10 and 19, plain or with a fused degree-1 column (+32, up to 10),
+        // single-chunk CN items only as 64+37 / 64+38; VN degrees 1..30, chunk pairs (+32) up to degree 12
+        if (!phase) {
+          const int dgr = it.key & 31, fz = (it.key >> 5) & 1, single = (it.key >> 6) & 1;
+          const bool body = single ? (fz && (dgr == 5 || dgr == 6)) : ((dgr >= 3 && dgr <= 10) || (dgr == 19 && !fz));
+          if (!body) ok = false;
+        } else {
+          const int dgr = it.key & 31, pair = (it.key >> 5) & 1;
+          if (dgr < 1 || dgr > 30 || (pair && dgr > 12)) ok = false;
+        }
+        tot += it.cost;
+        per[wv].push_back(it);
+      }
+      longest = std::max(longest, tot);
+    }
+    if (!ok) break;
+    std::vector<int32_t>& gl = phase ? g_vn : g_cn;
+    std::vector<int32_t>& il = phase ? i_vn : i_cn;
+    for (int wv = 0; wv < nwv; ++wv) {
+      g_ptr.push_back((int32_t)gl.size() / 2);
+      // groups by type, the type with the most expensive items first; the group order is rotated by the wave's index
+      // on its SIMD so that the four waves of a SIMD start a phase in different bodies (cf. lpt_schedule)
+      std::stable_sort(per[wv].begin(), per[wv].end(), [](const It& a, const It& b) {
+        return a.cost != b.cost ? a.cost > b.cost : a.key > b.key; });
+      std::vector<std::vector<It>> grp;
+      for (const It& it : per[wv]) {
+        if (grp.empty() || grp.back().front().key != it.key) {
+          size_t k2 = 0;
+          for (; k2 < grp.size(); ++k2)
+            if (grp[k2].front().key == it.key) break;
+          if (k2 == grp.size()) grp.emplace_back();
+          grp[k2].push_back(it);
+        } else {
+          grp.back().push_back(it);
+        }
+      }
+      if (grp.size() > 1) std::rotate(grp.begin(), grp.begin() + ((wv >> 2) % grp.size()), grp.end());
+      double rem = 0.0;
+      for (auto& gq : grp)
+        for (auto& it : gq) rem += it.cost;
+      for (auto& gq : grp) {
+        const size_t first = il.size() / 2;
+        for (auto& it : gq) {
+          const int prio = std::max(0, std::min(3, (int)std::ceil(4.0 * rem / longest) - 1));   // as item_priorities, ldpc5g.h
+          rem -= it.cost;
+          il.push_back(it.x | (prio << 24));
+          il.push_back(it.y);
+          (phase ? plan->vn : plan->cn)[wv].push_back(JitItem{it.idx, it.q, it.pr ? 2 : 1, prio});
+        }
+        gl.push_back(gq.front().key);
+        gl.push_back((int32_t)(first | ((il.size() / 2) << 16)));
+      }
+    }
+    g_ptr.push_back((int32_t)gl.size() / 2);
+    if (il.size() / 2 >= 65536) ok = false;
+  }
+  const int g_ok = ok && g_ptr.size() == (size_t)(2 * (nwv + 1)) ? 1 : 0;
+  if (g_ok) {
+    plan->z = z; plan->edges = b.edges; plan->ncu = ncu; plan->nbu = nbu;
+    plan->row_off.resize(ncu); plan->row_deg.resize(ncu); plan->fused_col.assign(fused_col.begin(), fused_col.begin() + ncu);
+    for (int r = 0; r < ncu; ++r) { plan->row_off[r] = b.row_off[r] & 0x3FFFF; plan->row_deg[r] = (int)by_row[r].size(); }
+    plan->col_edges.resize(nbu); plan->col_fused.assign(b.col_fused.begin(), b.col_fused.begin() + nbu);
+    for (int c = 0; c < nbu; ++c)
+      for (int i = 0; i < b.col_deg[c]; ++i)
+        plan->col_edges[c].push_back({b.col_ent2[b.col_start[c] + 2 * i], b.col_ent2[b.col_start[c] + 2 * i + 1]});
+    *plan_out = plan;
+  } else {
+    delete plan;
+  }
+  g_cn.resize(g_cn.size() + 2, 0); g_vn.resize(g_vn.size() + 2, 0);
+  i_cn.resize(i_cn.size() + 4, 0); i_vn.resize(i_vn.size() + 4, 0);
+  if (!g_ok) g_ptr.assign(2 * (nwv + 1), 0);
+  return g_ok;
+}
+
+int build_onchip_bp_tables(samd_ldpc5g* h, const BaseRows& by_row) {
+  MsBuild b;
+  b.z = h->z;
+  b.ncu = (h->n_cn + b.z - 1) / b.z; b.nbu = (h->n_vn + b.z - 1) / b.z;
+  b.chunks = (b.z + 63) / 64;
+  h->bp.ok = 0;
+  if (h->mb > 255 || h->nb > 255 || b.chunks > 255) return SAMD_OK;
+  if (!bp_message_layout(h, by_row, b)) return SAMD_OK;
+  std::vector<int32_t> cp, cl, vp, vl;
+  bp_item_lists(h, by_row, b, cp, cl, vp, vl);
+  ms_fused_and_tails(h, by_row, b);
+  ms_item_lists(h, by_row, b);
+  std::vector<int32_t> cl2, vl2, tail_tab, vtail_tab;
+  ms_encode_lists(by_row, b, cl2, vl2, tail_tab, vtail_tab);
+  h->ms.tail_sh = b.tail_sh;
   std::vector<int32_t> g_ptr, g_cn, g_vn, i_cn, i_vn;
   h->ms.g_ok = 0;
-  if (z % 128 == 0 && h->n_cn % z == 0 && h->n_vn % z == 0 && h->bp.waves == 16 && groups < 2) {
-    bool ok = true;
-    struct It { int cost, key; int32_t x, y; int idx, pr, q; };
-    JitPlan* plan = new JitPlan();
-    plan->cn.resize(h->bp.waves); plan->vn.resize(h->bp.waves);
-    auto cost_in = [](const std::vector<std::pair<int, int32_t>>& items, int32_t id) {
-      for (auto& it : items)
-        if (it.second == id) return it.first;
-      return 0;
-    };
-    const int nwv = h->bp.waves;
-    for (int phase = 0; phase < 2 && ok; ++phase) {
-      const std::vector<int32_t>& lp = phase ? mvp : mcp;
-      const std::vector<int32_t>& ll = phase ? mvl : mcl;
-      std::vector<std::vector<It>> per(nwv);
-      double longest = 1.0;
-      for (int wv = 0; wv < nwv; ++wv) {
-        double tot = 0.0;
-        for (int j = lp[wv]; j < lp[wv + 1]; ++j) {
-          const int32_t d = ll[j];
-          if ((d >> 25) & 1) { ok = false; break; }
-          const int idx = d & 0xFF, q = (d >> 8) & 0xFF, pr = (d >> 24) & 1;
-          It it;
-          it.idx = idx; it.pr = pr; it.q = q;
-          it.cost = cost_in(phase ? vi2 : ci2, d) + 3;
-          if (!phase) {
-            const int f = fused_col[idx] >= 0;
-            it.key = (int)by_row[idx].size() | (f << 5) | (pr ? 0 : 64);      // (64: a single chunk of the row)
-            it.x = (row_off[idx] & 0x3FFFF) + 256 * q;
-            it.y = f ? fused_col[idx] * z + q * 64 : 0;
-          } else {
-            it.key = col_deg[idx] | (pr << 5);
-            it.x = (idx * z + q * 64) | (pr << 23);
-            it.y = col_start[idx] | (q << 20);
-            if (col_start[idx] >= (1 << 20) || idx * z + q * 64 >= (1 << 23)) ok = false;
-          }
-          // every key must have a compiled body in ldpc5g_decode_msg_kernel (its switches end in `default: break`, which
-          // would skip the item silently): CN degrees 3..10 and 19, plain or with a fused degree-1 column (+32, up to 10),
-          // single-chunk CN items only as 64+37 / 64+38; VN degrees 1..30, chunk pairs (+32) up to degree 12
-          if (!phase) {
-            const int dgr = it.key & 31, fz = (it.key >> 5) & 1, single = (it.key >> 6) & 1;
-            const bool body = single ? (fz && (dgr == 5 || dgr == 6)) : ((dgr >= 3 && dgr <= 10) || (dgr == 19 && !fz));
-            if (!body) ok = false;
-          } else {
-            const int dgr = it.key & 31, pair = (it.key >> 5) & 1;
-            if (dgr < 1 || dgr > 30 || (pair && dgr > 12)) ok = false;
-          }
-          tot += it.cost;
-          per[wv].push_back(it);
-        }
-        longest = std::max(longest, tot);
-      }
-      if (!ok) break;
-      std::vector<int32_t>& gl = phase ? g_vn : g_cn;
-      std::vector<int32_t>& il = phase ? i_vn : i_cn;
-      for (int wv = 0; wv < nwv; ++wv) {
-        g_ptr.push_back((int32_t)gl.size() / 2);
-        // groups by type, the type with the most expensive items first; the group order is rotated by the wave's index
-        // on its SIMD so that the four waves of a SIMD start a phase in different bodies (cf. SAMD_MS_ORDER above)
-        std::stable_sort(per[wv].begin(), per[wv].end(), [](const It& a, const It& b) {
-          return a.cost != b.cost ? a.cost > b.cost : a.key > b.key; });
-        std::vector<std::vector<It>> grp;
-        for (const It& it : per[wv]) {
-          if (grp.empty() || grp.back().front().key != it.key) {
-            size_t k2 = 0;
-            for (; k2 < grp.size(); ++k2)
-              if (grp[k2].front().key == it.key) break;
-            if (k2 == grp.size()) grp.emplace_back();
-            grp[k2].push_back(it);
-          } else {
-            grp.back().push_back(it);
-          }
-        }
-        if (grp.size() > 1 && !opt_set("SAMD_MS_NOROT")) std::rotate(grp.begin(), grp.begin() + ((wv >> 2) % grp.size()), grp.end());
-        double rem = 0.0;
-        for (auto& gq : grp)
-          for (auto& it : gq) rem += it.cost;
-        for (auto& gq : grp) {
-          const size_t first = il.size() / 2;
-          for (auto& it : gq) {
-            const int prio = opt_set("SAMD_MS_NOPRIO") ? 0 : std::max(0, std::min(3, (int)std::ceil(4.0 * rem / longest) - 1));
-            rem -= it.cost;
-            il.push_back(it.x | (prio << 24));
-            il.push_back(it.y);
-            (phase ? plan->vn : plan->cn)[wv].push_back(JitItem{it.idx, it.q, it.pr ? 2 : 1, prio});
-          }
-          gl.push_back(gq.front().key);
-          gl.push_back((int32_t)(first | ((il.size() / 2) << 16)));
-        }
-      }
-      g_ptr.push_back((int32_t)gl.size() / 2);
-      if (il.size() / 2 >= 65536) ok = false;
-    }
-    h->ms.g_ok = ok && g_ptr.size() == (size_t)(2 * (nwv + 1)) ? 1 : 0;
-    if (h->ms.g_ok) {
-      // the same schedule as data for the source generator of the specialised kernel (ldpc5g_jit.cpp)
-      plan->z = z; plan->edges = edges; plan->ncu = ncu; plan->nbu = nbu;
-      plan->row_off.resize(ncu); plan->row_deg.resize(ncu); plan->fused_col.assign(fused_col.begin(), fused_col.begin() + ncu);
-      for (int r = 0; r < ncu; ++r) { plan->row_off[r] = row_off[r] & 0x3FFFF; plan->row_deg[r] = (int)by_row[r].size(); }
-      plan->col_edges.resize(nbu); plan->col_fused.assign(col_fused.begin(), col_fused.begin() + nbu);
-      for (int c = 0; c < nbu; ++c)
-        for (int i = 0; i < col_deg[c]; ++i)
-          plan->col_edges[c].push_back({col_ent2[col_start[c] + 2 * i], col_ent2[col_start[c] + 2 * i + 1]});
-      h->jit_plan = plan;
-    } else {
-      delete plan;
-    }
-    g_cn.resize(g_cn.size() + 2, 0); g_vn.resize(g_vn.size() + 2, 0);
-    i_cn.resize(i_cn.size() + 4, 0); i_vn.resize(i_vn.size() + 4, 0);
-    if (!h->ms.g_ok) g_ptr.assign(2 * (nwv + 1), 0);
-  }
-  int rc = h->bp.row_off.assign(row_off);
+  if (b.z % 128 == 0 && h->n_cn % b.z == 0 && h->n_vn % b.z == 0 && h->bp.waves == 16 && b.groups < 2)
+    h->ms.g_ok = ms_grouped_dispatch(h, by_row, b, g_ptr, g_cn, g_vn, i_cn, i_vn, &h->jit_plan);
+  int rc = h->bp.row_off.assign(b.row_off);
   if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.g_ptr.assign(g_ptr);
   if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.g_cn.assign(g_cn);
   if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.g_vn.assign(g_vn);
   if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.i_cn.assign(i_cn);
   if (rc == SAMD_OK && h->ms.g_ok) rc = h->ms.i_vn.assign(i_vn);
-  if (rc == SAMD_OK) rc = h->bp.col_ent.assign(col_ent);
-  if (rc == SAMD_OK) rc = h->ms.col_ent.assign(col_ent2);
-  if (rc == SAMD_OK) rc = h->ms.cn_ptr.assign(mcp);
-  if (rc == SAMD_OK) rc = h->ms.vn_ptr.assign(mvp);
+  if (rc == SAMD_OK) rc = h->bp.col_ent.assign(b.col_ent);
+  if (rc == SAMD_OK) rc = h->ms.col_ent.assign(b.col_ent2);
+  if (rc == SAMD_OK) rc = h->ms.cn_ptr.assign(b.mcp);
+  if (rc == SAMD_OK) rc = h->ms.vn_ptr.assign(b.mvp);
   if (rc == SAMD_OK) rc = h->ms.cn_list.assign(cl2);
   if (rc == SAMD_OK) rc = h->ms.vn_list.assign(vl2);
   if (rc == SAMD_OK) rc = h->ms.tail_tab.assign(tail_tab);
   if (rc == SAMD_OK) rc = h->ms.vtail_tab.assign(vtail_tab);
-  if (rc == SAMD_OK) rc = h->bp.col_deg.assign(col_deg);
+  if (rc == SAMD_OK) rc = h->bp.col_deg.assign(b.col_deg);
   if (rc == SAMD_OK) rc = h->bp.cn_ptr.assign(cp);
   if (rc == SAMD_OK) rc = h->bp.cn_list.assign(cl);
   if (rc == SAMD_OK) rc = h->bp.vn_ptr.assign(vp);

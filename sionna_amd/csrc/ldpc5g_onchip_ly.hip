@@ -106,7 +106,7 @@ __device__ __forceinline__ void ly_cn_row(unsigned a0, unsigned z4, const int32_
   }
   SAMD_LY_SUB(1)
   if constexpr (MODE == SAMD_CN_MINSUM) {
-    ms_minsum_inplace<D, 1, 1>(v, llr_max, offset);
+    ms_minsum_inplace<D, 1>(v, llr_max, offset);
   } else {
     // boxplus rules: bp_math.h's node update on the D messages of a chunk - the function of every other engine
     cn_update_col<MODE, D>(v[0], D, llr_max, 0.f);
@@ -412,14 +412,30 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_ly_kernel(
 
 // ------------------------------------------------------------------------------------------------ host tables
 int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
+  // ---- the schedule's constants, each with the measurement that chose it
+  // Lifting sizes below this stay on the HBM-resident engine, which runs many codewords side by side: Z = 11 is a tie,
+  // 7.8 against 8.1 M decodes/s; from Z = 18 on the on-chip engine with 4 waves per codeword wins, 5.2 against 3.9 M -
+  // layered_rate_smallz_r03z.txt
+  constexpr int kMinZ = 16;
+  // Cost model in cycles of a lone wave: a re-sum of n edges (rounded up to 4) costs kVnSlope n + kVnOvh per chunk, a whole
+  // check-node item of degree d kCnSlope d + kCnOvh (profiles/r03b/ly_grid_r03z.txt, profiles/r04b/ly_grid_r04.txt)
+  constexpr long kVnSlope = 18, kVnOvh = 250, kCnSlope = 60, kCnOvh = 300;
+  // Largest column degree whose two full chunks form one pair unit.  Two-chunk lifting sizes with the split lists of the
+  // boxplus rules: 8 is +0.9 % over 12 at C2, ly_grid_r03z.txt; with more chunks 12 stays - k=3000 n=6000, Z = 320, loses
+  // 2 % (boxplus-phi 7 %) with 8.  Whole-item lists under the SIMD-aware schedule of round 4: 12 is +0.7 % over 8 at C2,
+  // profiles/r04b/ly_pair_max.txt - a pair halves the walker's share per chunk, and the steps are bound by the SIMD's
+  // instruction total, not by the longest wave
+  constexpr int kPairMaxSplit2 = 8, kPairMax = 12;
+  // Weights (percent) of a SIMD's summed load - waves w, w + 4, ... share one issue pipe - in the ownership objective
+  // (beta) and against the busiest wave of a step (alpha), whole-item lists only: 45 and 10 are worth +3.9 % at C2 (653 ->
+  // 678 k decodes/s, profiles/r04b/ly_simd_*.txt); the split lists of the boxplus rules lose 1 % with them and keep 0
+  constexpr long kSimdBetaWhole = 10, kSimdAlphaWhole = 45;
+
   h->ly.ok = 0;
   const int z = h->z;
   const int ncu = (h->n_cn + z - 1) / z, nbu = (h->n_vn + z - 1) / z;
-  // (lifting sizes below 16 stay on the HBM-resident engine, which runs many codewords side by side: Z = 11 is a tie,
-  // 7.8 against 8.1 M decodes/s; from Z = 18 on the on-chip engine with 4 waves per codeword wins, 5.2 against 3.9 M -
-  // layered_rate_smallz_r03z.txt)
   if (h->n_cn % z != 0 || h->n_vn % z != 0 || h->mb > 255 || h->nb > 255 || nbu > 0xFFFF ||
-      z < ((int)opt_int("SAMD_LY_MINZ", 16)) || z > 64 * 255) return SAMD_OK;
+      z < kMinZ || z > 64 * 255) return SAMD_OK;
   static const int degs[] = {3, 4, 5, 6, 7, 8, 9, 10, 19};
   std::vector<int> col_deg(h->nb, 0);
   for (int r = 0; r < ncu; ++r)
@@ -438,7 +454,7 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
     if (col_deg[c] == 1 && sft == 0 && d >= 3 && d <= 10) { fused_col[r] = c; col_fused[c] = 1; ext_of_row[r] = n_ext++; }
   }
   // groups of consecutive rows that share no non-fused column
-  const std::vector<std::vector<int>> groups = layered_row_groups(by_row, ncu, h->nb, col_fused, opt_set("SAMD_LY_NOGROUP"));
+  const std::vector<std::vector<int>> groups = layered_row_groups(by_row, ncu, h->nb, col_fused);
   const int G = (int)groups.size();
   std::vector<std::vector<char>> in_group(G, std::vector<char>(h->nb, 0));
   for (int g = 0; g < G; ++g)
@@ -571,24 +587,15 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
     bool need = false;
     for (int c = 0; c < nbu; ++c)
       if (in_group[g][c] && (g + 1 == G || in_group[g + 1][c])) need = true;
-    if (need || opt_set("SAMD_LY_NODEFER")) ++nsteps;
+    if (need) ++nsteps;
   }
   // VN units: a column's chunk (or pair of chunks for degree <= 8 / 12); its item after the update of edge j reads 1 + (the
   // edges below j) messages.  Units go, heaviest first, to the wave where they add least to the sum over the groups of
   // the squared load.
   struct Unit { int c, q, pair, wave, slot; long cost; };
   std::vector<Unit> units;
-  // (cost model of the schedule, in cycles of a lone wave; development knobs for tools/ly_grid.py)
-  const long ly_vn_slope = opt_int("SAMD_LY_VN_SLOPE", 18);
-  const long ly_vn_ovh = opt_int("SAMD_LY_VN_OVH", 250);
-  const long ly_cn_slope = opt_int("SAMD_LY_CN_SLOPE", 60);
-  const long ly_cn_ovh = opt_int("SAMD_LY_CN_OVH", 300);
-  auto item_cost = [&](int c, int j, int pair) { return (pair ? 2 : 1) * ly_vn_slope * ((col_deg[c] - j + 3) / 4 * 4) + ly_vn_ovh; };
-  // (two-chunk lifting sizes with the split lists of the boxplus rules: 8 is +0.9 % over 12 at C2, ly_grid_r03z.txt; with
-  // more chunks 12 stays - k=3000 n=6000, Z = 320, loses 2 % (boxplus-phi 7 %) with 8.  Whole-item lists under the
-  // SIMD-aware schedule of round 4: 12 is +0.7 % over 8 at C2, profiles/r04b/ly_pair_max.txt - a pair halves the walker's
-  // share per chunk, and the steps are bound by the SIMD's instruction total, not by the longest wave)
-  const int pair_max = (int)opt_int("SAMD_LY_PAIR_MAX", (chunks == 2 && split ? 8 : 12));
+  auto item_cost = [&](int c, int j, int pair) { return (pair ? 2 : 1) * kVnSlope * ((col_deg[c] - j + 3) / 4 * 4) + kVnOvh; };
+  const int pair_max = chunks == 2 && split ? kPairMaxSplit2 : kPairMax;
   for (int c = 0; c < nbu; ++c) {
     if (xt_of_col[c] < 0) continue;
     for (int q = 0; q < chunks; ++q) {
@@ -603,8 +610,8 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   for (size_t i = 0; i < units.size(); ++i) order[i] = (int)i;
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return units[x].cost > units[y].cost; });
   std::vector<std::vector<long>> load(groups.size(), std::vector<long>(NW, 0));
-  // (the same objective per SIMD - waves w, w + 4, ... share one issue pipe - weighted by simd_beta percent; development knob)
-  const long simd_beta = opt_int("SAMD_LY_SIMD_BETA", split ? 0 : 10);
+  // (the same objective per SIMD, weighted by simd_beta percent)
+  const long simd_beta = split ? 0 : kSimdBetaWhole;
   std::vector<std::array<long, 4>> sload_g(groups.size(), std::array<long, 4>{0, 0, 0, 0});
   std::vector<int> vn_slots(NW, 0);
   std::vector<std::vector<int>> vn_slot_llr(NW);
@@ -663,20 +670,19 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
         sload[st][wv] += 500 + 350L * ((pt.ne + 1) / 2) + 8L * d;
       } else {
         step_items[st][wv].push_back({1L << 40, LY_CN | ((d | (f << 5)) << 2) | (q << 16), row_off[r], 4 * row_start[r], sidx});
-        sload[st][wv] += split ? 300 + 330L * ((d + 1) / 2) : ly_cn_ovh + ly_cn_slope * d;
+        sload[st][wv] += split ? 300 + 330L * ((d + 1) / 2) : kCnOvh + kCnSlope * d;
       }
       smax[st] = std::max(smax[st], sload[st][wv]);
     }
   struct VTask { int unit, j, lo, hi; long cost; };
   std::vector<VTask> vt;
-  const bool defer = !(opt_int("SAMD_LY_NODEFER", 0));
   for (size_t ui = 0; ui < units.size(); ++ui) {
     const Unit& u = units[ui];
     for (size_t k2 = 0; k2 < touch[u.c].size(); ++k2) {
       const int g0 = touch[u.c][k2].first, j = touch[u.c][k2].second;
       const int hi = (k2 + 1 < touch[u.c].size()) ? cn_step[touch[u.c][k2 + 1].first] - 1 : nsteps - 1;
       if (hi < cn_step[g0] + 1) return 1;                                  // (cannot happen: such a column got a step)
-      vt.push_back({(int)ui, j, cn_step[g0] + 1, defer ? hi : cn_step[g0] + 1, item_cost(u.c, j, u.pair)});
+      vt.push_back({(int)ui, j, cn_step[g0] + 1, hi, item_cost(u.c, j, u.pair)});
     }
   }
   std::stable_sort(vt.begin(), vt.end(), [](const VTask& x, const VTask& y) {
@@ -685,10 +691,8 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   // A step lasts as long as its busiest WAVE (a lone wave issues a dependent instruction every ~6.5 cycles) - or as its
   // busiest SIMD: wave w runs on SIMD w % 4, which issues one wave64 operation per 4 cycles for all its waves together, so
   // a re-sum placed beside a check-node item of the same SIMD slows that item down (profiles/r04b/layered_owed_*.txt).
-  // simd_alpha (percent; development knob, 0 = waves only) weighs the SIMD's summed load against the busiest wave's:
-  // 45 (+ simd_beta 10 in the ownership objective above) is worth +3.9 % at C2 for the whole-item lists (653 -> 678 k
-  // decodes/s, profiles/r04b/ly_simd_*.txt); the split lists of the boxplus rules lose 1 % with it and keep 0.
-  const long simd_alpha = opt_int("SAMD_LY_SIMD_ALPHA", split ? 0 : 45);
+  // simd_alpha (percent, 0 = waves only) weighs the SIMD's summed load against the busiest wave's.
+  const long simd_alpha = split ? 0 : kSimdAlphaWhole;
   std::vector<std::array<long, 4>> simd(nsteps, std::array<long, 4>{0, 0, 0, 0});
   for (int st = 0; st < nsteps; ++st)
     for (int wv = 0; wv < NW; ++wv) simd[st][wv & 3] += sload[st][wv];
@@ -805,12 +809,11 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
   Lists whole, parts;
   int NW = 0;
   for (int nw : {4, 8, 16}) {
-    if (opt_set("SAMD_LY_WAVES") && (int)opt_int("SAMD_LY_WAVES", 0) != nw) continue;
-    else if (nw < 16 && ((int)lds + max_scr) * (16 / nw) > 160 * 1024) continue;
+    if (nw < 16 && ((int)lds + max_scr) * (16 / nw) > 160 * 1024) continue;
     if (build_lists(false, nw, whole) == 0) { NW = nw; break; }
   }
   if (NW == 0) return SAMD_OK;
-  const bool have_parts = abl == 0 && !opt_set("SAMD_LY_NOSPLIT") && build_lists(true, NW, parts) == 0 && parts.scratch_bytes > 0;
+  const bool have_parts = abl == 0 && build_lists(true, NW, parts) == 0 && parts.scratch_bytes > 0;
   h->ly.waves = NW;
   h->ly.lds_bytes = (int)lds;
   h->ly.zero_off = zero_base / 4;

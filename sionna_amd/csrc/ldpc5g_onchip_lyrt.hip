@@ -58,7 +58,7 @@ __device__ __forceinline__ void lyrt_cn_row(unsigned ra, unsigned z4, const int3
   for (int i = 0; i < NF; ++i) t[i] = t[i] - lyrt_sent(a1o, a2o, wo, i);     // unclipped (a degree-1 node: t = llr as loaded)
 #pragma unroll
   for (int i = 0; i < D; ++i) v[0][i] = ms_med3(t[i], -llr_max, llr_max);
-  ms_minsum_inplace<D, 1, 1>(v, llr_max, offset);                             // v <- the messages sent now
+  ms_minsum_inplace<D, 1>(v, llr_max, offset);                             // v <- the messages sent now
   // their record: smaller / larger magnitude, first edge with the larger one, sign bits
   float a1 = fabsf(v[0][0]), a2 = a1;
   unsigned idx = 0u, sg = __float_as_uint(v[0][0]) >> 31;
@@ -187,7 +187,7 @@ int build_onchip_lyrt_tables(samd_ldpc5g* h, const BaseRows& by_row) {
     if (f) col_private[by_row[r][d - 1].first] = 1;
     key[r] = d | (f << 5);
   }
-  const std::vector<std::vector<int>> groups = layered_row_groups(by_row, ncu, h->nb, col_private, false);
+  const std::vector<std::vector<int>> groups = layered_row_groups(by_row, ncu, h->nb, col_private);
   const int chunks = (z + 63) / 64;                          // (the last one partly filled when Z is not a multiple of 64)
   // one slot: a block per column, three per row - a multiple of 4 Z bytes, which keeps every block aligned to 4 Z (the
   // power-of-two lifting sizes form an address as (position mod 4 Z) | block offset)

@@ -42,8 +42,9 @@ __device__ __forceinline__ float ms_med3(float a, float b, float c) { return __b
 
 // min-sum / offset-min-sum check-node arithmetic on the D incoming messages of NCH chunks, in place (v <- c2v):
 // second minimum with multiplicity, (m2 - m1) + m1 for a unique minimum (decoding.py:863), no -0 magnitudes.  The layered
-// engine (ldpc5g_onchip_ly.hip) calls it; ms_cn_row below holds the same operations with the fused degree-1 column in.
-template <int D, int NCH, int VAR>
+// engines (ldpc5g_onchip_ly.hip, ldpc5g_onchip_lyrt.hip) call it; ms_cn_row below holds the same operations (its VAR 1)
+// with the fused degree-1 column in.
+template <int D, int NCH>
 __device__ __forceinline__ void ms_minsum_inplace(float (&v)[NCH][D], float llr_max, float offset) {
   float m1[NCH], m2[NCH];
   unsigned sx[NCH];
@@ -55,8 +56,7 @@ __device__ __forceinline__ void ms_minsum_inplace(float (&v)[NCH][D], float llr_
     for (int h = 0; h < NCH; ++h) {
       m2[h] = __builtin_amdgcn_fmed3f(m1[h], m2[h], fabsf(v[h][i]));
       m1[h] = __builtin_amdgcn_fmed3f(m1[h], fabsf(v[h][i]), 0.f);
-      if (VAR == 0) sx[h] ^= __float_as_uint(v[h][i]);
-      else if (i & 1) sx[h] = __builtin_amdgcn_bitop3_b32(sx[h], __float_as_uint(v[h][i - 1]), __float_as_uint(v[h][i]), 0x96);
+      if (i & 1) sx[h] = __builtin_amdgcn_bitop3_b32(sx[h], __float_as_uint(v[h][i - 1]), __float_as_uint(v[h][i]), 0x96);
       else if (i == D - 1) sx[h] ^= __float_as_uint(v[h][i]);
     }
   float a1[NCH], a2[NCH];
@@ -65,23 +65,16 @@ __device__ __forceinline__ void ms_minsum_inplace(float (&v)[NCH][D], float llr_
     const float min_e = (m2[h] > m1[h]) ? ((m2[h] - m1[h]) + m1[h]) : m1[h];
     a1[h] = __builtin_amdgcn_fmed3f(m1[h] - offset, 0.f, llr_max);
     a2[h] = __builtin_amdgcn_fmed3f(min_e - offset, 0.f, llr_max);
-    if (VAR == 1) {
-      sx[h] &= 0x80000000u;
-      a1[h] = __uint_as_float(__float_as_uint(a1[h]) | sx[h]);
-      a2[h] = __uint_as_float(__float_as_uint(a2[h]) | sx[h]);
-    }
+    sx[h] &= 0x80000000u;
+    a1[h] = __uint_as_float(__float_as_uint(a1[h]) | sx[h]);
+    a2[h] = __uint_as_float(__float_as_uint(a2[h]) | sx[h]);
   }
 #pragma unroll
   for (int i = 0; i < D; ++i)
 #pragma unroll
     for (int h = 0; h < NCH; ++h) {
       const float mag = (fabsf(v[h][i]) == m1[h]) ? a2[h] : a1[h];
-      if (VAR == 1) {
-        v[h][i] = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(mag), __float_as_uint(v[h][i]), 0x80000000u, 0x78));
-      } else {
-        const unsigned sg = (__float_as_uint(v[h][i]) ^ sx[h]) & 0x80000000u;
-        v[h][i] = __uint_as_float(sg | __float_as_uint(mag));
-      }
+      v[h][i] = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(mag), __float_as_uint(v[h][i]), 0x80000000u, 0x78));
     }
 }
 
@@ -99,7 +92,8 @@ __device__ __forceinline__ void ms_minsum_inplace(float (&v)[NCH][D], float llr_
 // the offset fields of the DS instructions (no address arithmetic, D - 1 registers less).
 // VAR 1: gfx950's three-input bit operation (v_bitop3_b32) in the sign arithmetic - the node sign as one xor3 per TWO
 // edges, the row sign folded into the two candidate magnitudes once per row, own sign applied with sel ^ (v & msb) in
-// one operation: 5.5 instead of 7 vector operations per edge and chunk, the same bits.
+// one operation: 5.5 instead of 7 vector operations per edge and chunk, the same bits.  The grouped kernel's min-sum bodies
+// are VAR 1; the list-walking kernel (ldpc5g_decode_ms_kernel) keeps VAR 0, the two-input form.
 template <int D, int NCH, bool FUSE1, int MODE, unsigned Z4C = 0, int VAR = 0>
 __device__ __forceinline__ void ms_cn_row(unsigned a0, unsigned z4r, float llr_max, float offset,
                                           float* __restrict__ llr_v, bool last, unsigned phi_base = kPhiNoLds) {
@@ -553,7 +547,7 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_ms_kernel(
 //            edge table | chunk << 20
 //   group    x = body type (CN: degree | fused << 5; VN: degree | pair << 5),  y = first item | (last + 1) << 16
 // ZM: 0 = any Z (multiple of 128), 1 = Z a power of two, 2 = Z = 128 (block stride and chunk flip at compile time)
-template <int ZM, bool LLRG, int MODE, int VAR>
+template <int ZM, bool LLRG, int MODE>
 __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
     const float* __restrict__ llr_in, float* __restrict__ out, float* __restrict__ llr_ws, RateMatch p, int n_cn,
     int nbu, int batch, int num_iter, float llr_max, float offset, int hard_out, int return_infobits,
@@ -567,6 +561,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
   const unsigned phi_base = (MODE == SAMD_CN_BOXPLUS_PHI && phi_lds) ? 4u * (unsigned)(msg_floats + (LLRG ? 0 : nbu * p.z)) : kPhiNoLds;
   if (phi_base != kPhiNoLds) { phi_tab_stage(phi_base, (int)threadIdx.x); __syncthreads(); }
   constexpr bool POW2 = ZM >= 1;
+  constexpr int VAR = MODE == SAMD_CN_MINSUM ? 1 : 0;                  // the bit-operation variant exists for min-sum only
   constexpr unsigned Z4C = ZM == 2 ? 512u : 0u;
   const unsigned z = ZM == 2 ? 128u : (unsigned)p.z, z4 = 4u * z;
   const unsigned zw = POW2 ? z4 - 1u : z4;
@@ -752,20 +747,16 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
     llr_ws = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
   }
   const bool pow2 = (h->z & (h->z - 1)) == 0;
-  if (h->ms.g_ok && h->bp.waves == 16 && !h->opt.ms_nogroup) {
+  if (h->ms.g_ok && h->bp.waves == 16) {
     // grouped dispatch: the same items, sorted by body type per wave (see ldpc5g_decode_msg_kernel)
     typedef void (*gkern_t)(const float*, float*, float*, RateMatch, int, int, int, int, float, float, int, int, int,
                             const int32_t*, const int32_t*, const int2*, const int32_t*, const int2*, const int2*,
                             const int2*, const int2*, int, int);
-    constexpr int V1 = MODE == SAMD_CN_MINSUM ? 1 : 0;        // the bit-operation variant exists for min-sum only
-#define SAMD_MSG_K(V) {ldpc5g_decode_msg_kernel<0, false, MODE, V>, ldpc5g_decode_msg_kernel<1, false, MODE, V>, \
-                       ldpc5g_decode_msg_kernel<2, false, MODE, V>, ldpc5g_decode_msg_kernel<0, true, MODE, V>,  \
-                       ldpc5g_decode_msg_kernel<1, true, MODE, V>,  ldpc5g_decode_msg_kernel<2, true, MODE, V>}
-    static const gkern_t gk[2][6] = {SAMD_MSG_K(0), SAMD_MSG_K(V1)};
-#undef SAMD_MSG_K
-    const int zm = (h->z == 128 && !h->opt.ms_noz128) ? 2 : (pow2 ? 1 : 0);
-    const int var = h->opt.ms_var;                             // bit-operation variant: default
-    const gkern_t fn = gk[var][(h->bp.llr_global ? 3 : 0) + zm];
+    static const gkern_t gk[6] = {ldpc5g_decode_msg_kernel<0, false, MODE>, ldpc5g_decode_msg_kernel<1, false, MODE>,
+                                  ldpc5g_decode_msg_kernel<2, false, MODE>, ldpc5g_decode_msg_kernel<0, true, MODE>,
+                                  ldpc5g_decode_msg_kernel<1, true, MODE>,  ldpc5g_decode_msg_kernel<2, true, MODE>};
+    const int zm = h->z == 128 ? 2 : (pow2 ? 1 : 0);
+    const gkern_t fn = gk[(h->bp.llr_global ? 3 : 0) + zm];
     SAMD_SET_MAX_LDS(fn, 160 * 1024);
     const int nbu_g = (h->n_vn + h->z - 1) / h->z;
     const RateMatch rm_g = make_rate_match(h);
@@ -782,7 +773,8 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
                        reinterpret_cast<const int2*>(h->ms.vn_list.get()), h->ms.g_ptr.get(),
                        reinterpret_cast<const int2*>(h->ms.g_cn.get()), reinterpret_cast<const int2*>(h->ms.g_vn.get()),
                        reinterpret_cast<const int2*>(h->ms.i_cn.get()), reinterpret_cast<const int2*>(h->ms.i_vn.get()),
-                       h->opt.ms_ldsbar, phi_lds_g);
+                       /* lds_bar: always the full barrier - the argument stays because the kernels' register allocation
+                          moves without it */ 0, phi_lds_g);
     return launch_status();
   }
   typedef void (*kern_t)(const float*, float*, float*, RateMatch, int, int, int, int, float, float, int, int, int,

@@ -10,7 +10,13 @@ meant to leave the choice alone must reproduce it exactly.  INTEGRATION.md and t
 A host-only handle owns no device table, so min-sum never reports the explicit-message engine in that record.
 tests/golden/ldpc5g_selection_gpu.json is the same record for a few codes with handles on a device (written by the same
 tool with --device, from the same earlier library): codes whose messages fit LDS - min-sum engine 2, one of them with the
-channel LLRs in the workspace - and one that spills; test_device_selection_matches_the_record (gpu) holds it."""
+channel LLRs in the workspace - and one that spills; test_device_selection_matches_the_record (gpu) holds it.
+
+tests/golden/ldpc5g_tables.json (the same tool with --tables, the same grid) records what the table builders PRODUCE: per
+code the 64-bit digest samd_debug_table_digest returns after samd_ldpc5g_create of a host-only handle - every device table
+of every engine (element size, count, bytes, in build order) and the engines' scalars.  It was written from the library of
+the commit before the tuning options of the hand-written engines were retired (that commit plus the digest entry alone), so
+test_tables_match_the_record holds every schedule and table of those builders to what they were."""
 import json
 
 import pytest
@@ -21,6 +27,8 @@ with open(gen.FIXTURE) as _f:
     ROWS = json.load(_f)
 with open(gen.DEVICE_FIXTURE) as _f:
     DEVICE_ROWS = json.load(_f)
+with open(gen.TABLES_FIXTURE) as _f:
+    TABLE_ROWS = json.load(_f)
 GROUPS = sorted({(r["code"][0], r["none"][0]) for r in ROWS})          # (base graph, lifting size)
 
 
@@ -43,6 +51,24 @@ def test_selection_matches_the_record(bg, z):
         assert got is not None, r["code"]
         for sw in ("none",) + gen.SWITCHES:
             assert got[sw] == r.get(sw, r["none"]), (r["code"], sw)
+
+
+def test_tables_fixture_covers_the_grid():
+    assert [tuple(r["code"]) for r in TABLE_ROWS] == gen.codes()
+    assert sorted({(r["code"][0], r["z"]) for r in TABLE_ROWS}) == GROUPS
+    assert all(len(r["digest"]) == 16 and int(r["digest"], 16) >= 0 for r in TABLE_ROWS)
+    # the digest separates the codes: every (base graph, k, n) has tables of its own, and the output interleaver shows
+    # where the handle has a table for it (the bit-packed encoder's, lifting sizes that are multiples of 32)
+    plain = {tuple(r["code"][:3]): r["digest"] for r in TABLE_ROWS if r["code"][3] is None}
+    assert len(set(plain.values())) == len(plain) == len(TABLE_ROWS) // 2
+    assert any(r["code"][3] == 6 and r["digest"] != plain[tuple(r["code"][:3])] for r in TABLE_ROWS)
+
+
+@pytest.mark.parametrize("bg,z", GROUPS, ids=[f"{bg}-z{z}" for bg, z in GROUPS])
+def test_tables_match_the_record(bg, z):
+    for r in TABLE_ROWS:
+        if (r["code"][0], r["z"]) == (bg, z):
+            assert gen.table_digest(tuple(r["code"])) == [r["z"], r["digest"]], r["code"]
 
 
 MINSUM, OFFSET = 2, 3                                                   # cn_mode values (include/sionna_amd.h)
