@@ -894,6 +894,46 @@ int samd_rzf_precode_ofdm_c128(const double* x, const double* h, const double* a
                                int fft_size, int num_eff_sc, double* x_precoded, double* h_eff, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Precoded channels and the post-equalisation SINR (csrc/precoding.hip, csrc/post_eq_sinr.hip), complex64 (_c64) and
+ * complex128 (_c128, precision = "double").  Interleaved complex, row-major, naturally aligned.
+ *   samd_precoded_channel   RZFPrecodedChannel / CBFPrecodedChannel / EyePrecodedChannel.call (ofdm/precoding.py:417-446,
+ *                           486-510, 547-566 on the helpers of PrecodedChannel :246-369): h, h_hat [B,RX,RXA,TX,M,T,F]
+ *                           (h_hat may be h; not read in mode SAMD_PRECODE_EYE), alpha [B,TX,T,F] DEVICE or NULL and
+ *                           alpha0 (RZF only), tx_power [B,TX,K,T,F] DEVICE or NULL and tx_power0 for every stream;
+ *                           precoding_ind / eff_pos as for samd_rzf_precode_ofdm.  G is computed from h_hat
+ *                           (mode SAMD_PRECODE_RZF / _CBF) or is the identity (SAMD_PRECODE_EYE: K == M and
+ *                           precoding_ind is not read), column k is scaled by sqrt(tx_power[b,tx,k,t,f]), and
+ *                           h_eff [B,RX,RXA,TX,K,T,num_eff_sc] = H_r G for EVERY receiver r is formed from the TRUE h.
+ *                           1 <= K <= M, K <= 16, M <= 32; anything else returns SAMD_ERR_INVALID.
+ *   samd_lmmse_post_eq_sinr LMMSEPostEqualizationSINR.call (ofdm/equalization.py:800-839 on the helpers of
+ *                           PostEqualizationSINR :571-752, inv_cholesky utils/linalg.py:8-32 and lmmse_matrix without s,
+ *                           mimo/equalization.py:91-97): h_eff [B,RX,RXA,TX,K,T,Fe], no [B,RX,RXA,T,Fe] DEVICE or NULL
+ *                           and no0; desired_ind DEVICE int32 [RX, num_streams_per_rx] and undesired_ind DEVICE int32
+ *                           [RX, num_interfering_streams_per_rx] (may be NULL when that is 0): flat indices over
+ *                           [rx, tx, stream], each in [0, RX * TX * K) (StreamManagement.detection_desired_ind /
+ *                           detection_undesired_ind) -> sinr [B,T,Fe,RX,num_streams_per_rx] of the real type.
+ *                           num_rx_ant <= 16 and num_streams_per_rx <= 16; num_interfering_streams_per_rx has no cap.
+ * ---------------------------------------------------------------------------------- */
+#define SAMD_PRECODE_EYE 2
+int samd_precoded_channel_c64(const float* h, const float* h_hat, const float* alpha, float alpha0, const float* tx_power,
+                              float tx_power0, const int32_t* precoding_ind, const int32_t* eff_pos, int mode, int batch,
+                              int num_tx, int num_streams, int num_rx, int num_rx_ant, int num_tx_ant, int num_rx_per_tx,
+                              int num_ofdm_symbols, int fft_size, int num_eff_sc, float* h_eff, void* stream);
+int samd_precoded_channel_c128(const double* h, const double* h_hat, const double* alpha, double alpha0,
+                               const double* tx_power, double tx_power0, const int32_t* precoding_ind,
+                               const int32_t* eff_pos, int mode, int batch, int num_tx, int num_streams, int num_rx,
+                               int num_rx_ant, int num_tx_ant, int num_rx_per_tx, int num_ofdm_symbols, int fft_size,
+                               int num_eff_sc, double* h_eff, void* stream);
+int samd_lmmse_post_eq_sinr_c64(const float* h_eff, const float* no, float no0, const int32_t* desired_ind,
+                                const int32_t* undesired_ind, int interference_whitening, int batch, int num_rx,
+                                int num_rx_ant, int num_tx, int num_streams_per_tx, int num_ofdm_symbols, int num_eff_sc,
+                                int num_streams_per_rx, int num_interfering_streams_per_rx, float* sinr, void* stream);
+int samd_lmmse_post_eq_sinr_c128(const double* h_eff, const double* no, double no0, const int32_t* desired_ind,
+                                 const int32_t* undesired_ind, int interference_whitening, int batch, int num_rx,
+                                 int num_rx_ant, int num_tx, int num_streams_per_tx, int num_ofdm_symbols, int num_eff_sc,
+                                 int num_streams_per_rx, int num_interfering_streams_per_rx, double* sinr, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Convolutional codes (csrc/conv.hip), float32 (_f32) and float64 (_f64, precision = "double").
  * The code: polys HOST array of conv_n generator polynomials (bit constraint_length-1-i of polys[p] = character i of
  * the reference's 0/1 string, e.g. "1101" -> 13), 1 <= conv_n <= 8, constraint_length 3..8, rsc: the first polynomial

@@ -65,6 +65,10 @@ _SIGNATURES = {
     "samd_precoding_matrix_c128": (_i32, [_vp, _vp, _vp, _f64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "samd_rzf_precode_ofdm_c64": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp] + [_i32] * 10 + [_vp, _vp, _vp]),
     "samd_rzf_precode_ofdm_c128": (_i32, [_vp, _vp, _vp, _f64, _vp, _vp] + [_i32] * 10 + [_vp, _vp, _vp]),
+    "samd_precoded_channel_c64": (_i32, [_vp, _vp, _vp, _f32, _vp, _f32, _vp, _vp] + [_i32] * 11 + [_vp, _vp]),
+    "samd_precoded_channel_c128": (_i32, [_vp, _vp, _vp, _f64, _vp, _f64, _vp, _vp] + [_i32] * 11 + [_vp, _vp]),
+    "samd_lmmse_post_eq_sinr_c64": (_i32, [_vp, _vp, _f32, _vp, _vp] + [_i32] * 10 + [_vp, _vp]),
+    "samd_lmmse_post_eq_sinr_c128": (_i32, [_vp, _vp, _f64, _vp, _vp] + [_i32] * 10 + [_vp, _vp]),
     "samd_conv_encode_f32": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_conv_encode_f64": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_conv_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64, _i32]),

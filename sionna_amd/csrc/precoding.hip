@@ -4,6 +4,9 @@
 //   RZFPrecoder.call                      ofdm/precoding.py:118-177          gather of the intended receivers' channels,
 //                                         precoding, and the effective channel H_r G at the effective subcarriers
 //                                         (_compute_effective_channel :81-116 + RemoveNulledSubcarriers)
+//   RZF/CBF/EyePrecodedChannel.call       ofdm/precoding.py:417-446, 486-510, 547-566 (helpers :246-369): G from the
+//                                         channel knowledge h_hat (or the identity), column k times sqrt(tx_power_k), and
+//                                         the effective channel H_r G from the true h at the effective subcarriers
 // D = diag(1 / ||v_k||) normalises every column of G to unit norm; a zero column stays zero (divide_no_nan).
 //
 // One lane per item (an OFDM resource element (b, tx, t, f), f fastest, so that every load and store of a wave is
@@ -22,6 +25,7 @@ namespace {
 
 constexpr int kKMax = 16, kMMax = 32, kBlock = 128;
 constexpr int kModeRzf = 0, kModeCbf = 1;
+constexpr int kModeEye = 2;                              // precoded channels only: G = I (K == M)
 
 template <typename R> struct cx { R re, im; };
 template <typename R> __device__ __forceinline__ cx<R> C(R r, R i) { return cx<R>{r, i}; }
@@ -194,6 +198,80 @@ template <typename R, int KT, int MT> __global__ __launch_bounds__(kBlock) void 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// PrecodedChannel (RZF / CBF / identity): one lane per resource element (b, tx, t, f); only h_eff is written
+// ------------------------------------------------------------------------------------------------------------------
+template <typename R> struct PrecodedChannelArgs {
+  const R* h;          // [B, RX, RXA, TX, M, T, F] complex: the true channel, h_eff is formed from it
+  const R* h_hat;      // same shape: the channel knowledge G is computed from (may be h; unused in the identity mode)
+  const R* alpha;      // [B, TX, T, F] or nullptr (alpha0 everywhere); RZF only
+  R alpha0;
+  const R* tx_power;   // [B, TX, K, T, F] or nullptr (tx_power0 everywhere)
+  R tx_power0;
+  const int* pind;     // [TX, NRXT] (StreamManagement.precoding_ind; unused in the identity mode)
+  const int* fe_of_f;  // [F] index among the effective subcarriers, -1 for a nulled one
+  R* heff;             // [B, RX, RXA, TX, K, T, Fe] complex
+  int64_t n;           // B * TX * T * F
+  int RX, RXA, TX, M, K, NRXT, T, F, Fe, mode;
+};
+
+template <typename R, int KT, int MT>
+__global__ __launch_bounds__(kBlock) void precoded_channel_kernel(PrecodedChannelArgs<R> p) {
+  const int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (it >= p.n) return;
+  constexpr int KA = KT ? KT : kKMax, MA = MT ? MT : kMMax;
+  const int K = KT ? KT : p.K, M = MT ? MT : p.M;
+  constexpr int U = KT && MT ? 32 : 1;
+  const int64_t TF = (int64_t)p.T * p.F;
+  const int64_t tf = it % TF;
+  const int f = (int)(tf % p.F), t = (int)(tf / p.F);
+  const int fe = p.fe_of_f[f];
+  if (fe < 0) return;                                   // a nulled subcarrier has no entry in h_eff
+  const int64_t btx = it / TF;                          // b * TX + tx
+  const int tx = (int)(btx % p.TX);
+  const int64_t b = btx / p.TX;
+  auto hidx = [&](int r, int a, int m) -> int64_t { return ((((b * p.RX + r) * p.RXA + a) * p.TX + tx) * M + m) * TF + tf; };
+
+  cx<R> X[KA * MA], A[KA * KA];
+  if (p.mode == kModeEye) {
+#pragma unroll U
+    for (int k = 0; k < K; ++k)
+#pragma unroll U
+      for (int m = 0; m < M; ++m) X[k * M + m] = C<R>(k == m ? R(1) : R(0), R(0));
+  } else {
+#pragma unroll U
+    for (int k = 0; k < K; ++k) {
+      const int r = p.pind[tx * p.NRXT + k / p.RXA], a = k % p.RXA;
+#pragma unroll U
+      for (int m = 0; m < M; ++m) X[k * M + m] = ld(p.h_hat, hidx(r, a, m));
+    }
+    const R alpha = p.alpha ? p.alpha[it] : p.alpha0;
+    precoding_matrix<R, KT, MT>(X, A, K, M, alpha, p.mode);
+  }
+  // column k of G times sqrt(tx_power[b, tx, k, t, f]): a real square root, then real times complex
+#pragma unroll U
+  for (int k = 0; k < K; ++k) {
+    const R s = sqrt(p.tx_power ? p.tx_power[(btx * K + k) * TF + tf] : p.tx_power0);
+#pragma unroll U
+    for (int m = 0; m < M; ++m) X[k * M + m] = sc(X[k * M + m], s);
+  }
+  const int64_t TFe = (int64_t)p.T * p.Fe, tfe = (int64_t)t * p.Fe + fe;
+  for (int r = 0; r < p.RX; ++r)
+    for (int a = 0; a < p.RXA; ++a) {
+      cx<R> row[MA];
+#pragma unroll U
+      for (int m = 0; m < M; ++m) row[m] = ld(p.h, hidx(r, a, m));
+      const int64_t base = (((b * p.RX + r) * p.RXA + a) * p.TX + tx) * K;
+#pragma unroll U
+      for (int k = 0; k < K; ++k) {
+        cx<R> v = C<R>(R(0), R(0));
+#pragma unroll U
+        for (int m = 0; m < M; ++m) v = v + row[m] * X[k * M + m];
+        st(p.heff, (base + k) * TFe + tfe, v);
+      }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // mimo functions: n independent problems, h [n, K, M] -> g [n, M, K], x [n, K] -> x_precoded [n, M]
 // ------------------------------------------------------------------------------------------------------------------
 template <typename R> struct MatPrecodeArgs {
@@ -287,6 +365,49 @@ template <typename R> int precoding_matrix_launch(const MatPrecodeArgs<R>& p, vo
   return launch_status();
 }
 
+template <typename R> int precoded_channel(const PrecodedChannelArgs<R>& p, void* stream) {
+  SAMD_REQUIRE(p.h && p.fe_of_f && p.heff, "null argument");
+  SAMD_REQUIRE(p.mode == kModeRzf || p.mode == kModeCbf || p.mode == kModeEye, "PrecodedChannel: unknown mode");
+  SAMD_REQUIRE(p.n >= 0 && p.RX >= 1 && p.RXA >= 1 && p.TX >= 1 && p.T >= 1 && p.F >= 1 && p.Fe >= 0 && p.Fe <= p.F,
+               "PrecodedChannel: invalid dimensions");
+  if (p.mode == kModeEye) {
+    SAMD_REQUIRE(p.K == p.M, "EyePrecodedChannel: num_streams_per_tx must equal num_tx_ant");
+  } else {
+    SAMD_REQUIRE(p.h_hat && p.pind, "null argument");
+    SAMD_REQUIRE(p.NRXT >= 1 && p.NRXT <= p.RX, "PrecodedChannel: more receivers per transmitter than receivers");
+    SAMD_REQUIRE(p.K == p.NRXT * p.RXA,
+                 "PrecodedChannel: num_streams_per_tx must equal (receivers per transmitter) x num_rx_ant");
+  }
+  const int rc = check_sizes(p.K, p.M, p.n);
+  if (rc != SAMD_OK) return rc;
+  if (p.n == 0 || p.Fe == 0) return SAMD_OK;
+  hipStream_t s = (hipStream_t)stream;
+#define SAMD_PC_CASE(KK, MM)                                                                                 \
+  if (p.K == KK && p.M == MM) {                                                                              \
+    hipLaunchKernelGGL((precoded_channel_kernel<R, KK, MM>), dim3(blocks(p.n)), dim3(kBlock), 0, s, p);      \
+    return launch_status();                                                                                  \
+  }
+  SAMD_PRECODING_SHAPES(SAMD_PC_CASE)
+#undef SAMD_PC_CASE
+  hipLaunchKernelGGL((precoded_channel_kernel<R, 0, 0>), dim3(blocks(p.n)), dim3(kBlock), 0, s, p);
+  return launch_status();
+}
+
+template <typename R>
+int precoded_channel_entry(const R* h, const R* h_hat, const R* alpha, R alpha0, const R* tx_power, R tx_power0,
+                           const int32_t* precoding_ind, const int32_t* eff_pos, int mode, int batch, int num_tx,
+                           int num_streams, int num_rx, int num_rx_ant, int num_tx_ant, int num_rx_per_tx,
+                           int num_ofdm_symbols, int fft_size, int num_eff_sc, R* h_eff, void* stream) {
+  SAMD_REQUIRE(batch >= 0, "PrecodedChannel: batch >= 0");
+  PrecodedChannelArgs<R> p;
+  p.h = h; p.h_hat = h_hat; p.alpha = alpha; p.alpha0 = alpha0; p.tx_power = tx_power; p.tx_power0 = tx_power0;
+  p.pind = precoding_ind; p.fe_of_f = eff_pos; p.heff = h_eff; p.mode = mode;
+  p.n = (int64_t)batch * num_tx * num_ofdm_symbols * fft_size;
+  p.RX = num_rx; p.RXA = num_rx_ant; p.TX = num_tx; p.M = num_tx_ant; p.K = num_streams; p.NRXT = num_rx_per_tx;
+  p.T = num_ofdm_symbols; p.F = fft_size; p.Fe = num_eff_sc;
+  return precoded_channel<R>(p, stream);
+}
+
 template <typename R>
 int rzf_ofdm_entry(const R* x, const R* h, const R* alpha, R alpha0, const int32_t* precoding_ind, const int32_t* eff_pos,
                    int batch, int num_tx, int num_streams, int num_rx, int num_rx_ant, int num_tx_ant, int num_rx_per_tx,
@@ -338,4 +459,23 @@ extern "C" int samd_precoding_matrix_c64(const float* h, const float* x, const f
 extern "C" int samd_precoding_matrix_c128(const double* h, const double* x, const double* alpha, double alpha0, int64_t n,
                                           int k, int m, int mode, double* g, double* x_precoded, void* stream) {
   return matrix_entry<double>(h, x, alpha, alpha0, n, k, m, mode, g, x_precoded, stream);
+}
+
+extern "C" int samd_precoded_channel_c64(const float* h, const float* h_hat, const float* alpha, float alpha0,
+                                         const float* tx_power, float tx_power0, const int32_t* precoding_ind,
+                                         const int32_t* eff_pos, int mode, int batch, int num_tx, int num_streams,
+                                         int num_rx, int num_rx_ant, int num_tx_ant, int num_rx_per_tx, int num_ofdm_symbols,
+                                         int fft_size, int num_eff_sc, float* h_eff, void* stream) {
+  return precoded_channel_entry<float>(h, h_hat, alpha, alpha0, tx_power, tx_power0, precoding_ind, eff_pos, mode, batch,
+                                       num_tx, num_streams, num_rx, num_rx_ant, num_tx_ant, num_rx_per_tx, num_ofdm_symbols,
+                                       fft_size, num_eff_sc, h_eff, stream);
+}
+extern "C" int samd_precoded_channel_c128(const double* h, const double* h_hat, const double* alpha, double alpha0,
+                                          const double* tx_power, double tx_power0, const int32_t* precoding_ind,
+                                          const int32_t* eff_pos, int mode, int batch, int num_tx, int num_streams,
+                                          int num_rx, int num_rx_ant, int num_tx_ant, int num_rx_per_tx,
+                                          int num_ofdm_symbols, int fft_size, int num_eff_sc, double* h_eff, void* stream) {
+  return precoded_channel_entry<double>(h, h_hat, alpha, alpha0, tx_power, tx_power0, precoding_ind, eff_pos, mode, batch,
+                                        num_tx, num_streams, num_rx, num_rx_ant, num_tx_ant, num_rx_per_tx, num_ofdm_symbols,
+                                        fft_size, num_eff_sc, h_eff, stream);
 }

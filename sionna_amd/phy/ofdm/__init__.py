@@ -4,8 +4,9 @@ from .pilot_pattern import PilotPattern, EmptyPilotPattern, KroneckerPilotPatter
 from .resource_grid import ResourceGrid, ResourceGridMapper, ResourceGridDemapper, RemoveNulledSubcarriers
 from .channel_estimation import (LSChannelEstimator, NearestNeighborInterpolator, LinearInterpolator, LMMSEInterpolator,
                                  tdl_freq_cov_mat, tdl_time_cov_mat)
-from .equalization import OFDMEqualizer, LMMSEEqualizer, ZFEqualizer, MFEqualizer
+from .equalization import OFDMEqualizer, LMMSEEqualizer, ZFEqualizer, MFEqualizer, PostEqualizationSINR, \
+    LMMSEPostEqualizationSINR
 from .detection import LinearDetector, MMSEPICDetector, EPDetector, KBestDetector, MaximumLikelihoodDetector, \
     MaximumLikelihoodDetectorWithPrior
 from .modulator import OFDMModulator, OFDMDemodulator
-from .precoding import RZFPrecoder
+from .precoding import RZFPrecoder, PrecodedChannel, RZFPrecodedChannel, CBFPrecodedChannel, EyePrecodedChannel

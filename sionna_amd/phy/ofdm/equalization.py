@@ -1,7 +1,11 @@
 """OFDM MIMO equalisation - mirror of reference src/sionna/phy/ofdm/equalization.py
 (``OFDMEqualizer`` :17-275, ``LMMSEEqualizer`` :277-344).  The whole ``call`` (layout changes,
 interference-plus-noise covariance, per-RE LMMSE solve, stream re-ordering, data-symbol gather)
-is ONE HIP kernel, ``samd_ofdm_lmmse_c64`` (csrc/mimo.hip)."""
+is ONE HIP kernel, ``samd_ofdm_lmmse_c64`` (csrc/mimo.hip).  ``PostEqualizationSINR`` / ``LMMSEPostEqualizationSINR``
+(:464-839): the whole ``call`` of the latter is ONE launch of ``samd_lmmse_post_eq_sinr_c64`` / ``_c128``
+(csrc/post_eq_sinr.hip)."""
+from abc import abstractmethod
+
 import numpy as np
 import torch
 
@@ -243,3 +247,137 @@ class MFEqualizer(OFDMEqualizer):
 
     def __init__(self, resource_grid, stream_management, precision=None, **kwargs):
         super().__init__("mf", resource_grid, stream_management, precision=precision, **kwargs)
+
+
+class PostEqualizationSINR(Block):
+    """Abstract base class of the SINR of every stream after equalisation (ofdm/equalization.py:464-756).
+
+    ``call(h_eff, no, h_eff_hat=None)``: h_eff, h_eff_hat [B, num_rx, num_rx_ant, num_tx, num_streams_per_tx, T,
+    num_effective_subcarriers] (the output of a ``PrecodedChannel``), no [B, num_rx, num_rx_ant, T,
+    num_effective_subcarriers] or its first n dims -> sinr [B, T, num_effective_subcarriers, num_rx, num_streams_per_rx].
+
+    ``get_per_rx_channels``, ``compute_interference_covariance_matrix``, ``compute_desired_signal_power``,
+    ``compute_total_power``, ``compute_noise_power`` and ``compute_sinr`` are the reference's public helpers as plain
+    device tensor operations (not the hot path): a subclass with another combiner composes its ``call`` from them."""
+
+    def __init__(self, resource_grid, stream_management, precision=None, **kwargs):
+        super().__init__(precision=precision, **kwargs)
+        self._resource_grid, self._stream_management = resource_grid, stream_management
+
+    def get_per_rx_channels(self, h_eff):
+        """h_eff [B, rx, rxa, tx, K, T, Fe] -> (h_eff_desired [B, rx, T, Fe, rxa, num_streams_per_rx],
+        h_eff_undesired [B, rx, T, Fe, rxa, num_interfering_streams_per_rx]) (:571-623)"""
+        sm = self._stream_management
+        h_eff = _ffi.to_device(h_eff, self.cdtype)
+        flat = h_eff.permute(1, 3, 4, 0, 2, 5, 6)
+        flat = flat.reshape((-1,) + tuple(flat.shape[3:]))                           # [rx * tx * K, B, rxa, T, Fe]
+        out = []
+        for ind in (sm.detection_desired_ind, sm.detection_undesired_ind):
+            ind = torch.as_tensor(np.asarray(ind, np.int64), device=h_eff.device)
+            g = flat.index_select(0, ind)
+            g = g.reshape((sm.num_rx, ind.numel() // sm.num_rx) + tuple(g.shape[1:]))  # [rx, S or U, B, rxa, T, Fe]
+            out.append(g.permute(2, 0, 4, 5, 3, 1))
+        return out[0], out[1]
+
+    def compute_interference_covariance_matrix(self, no=None, h_eff_undesired=None):
+        """no [B, rx, T, Fe, rxa], h_eff_undesired [B, rx, T, Fe, rxa, U] -> s [B, rx, T, Fe, rxa, rxa] (:625-654)"""
+        s = 0.
+        if no is not None:
+            s = torch.diag_embed(_ffi.to_device(no, self.rdtype).to(self.cdtype))
+        if h_eff_undesired is not None:
+            hu = _ffi.to_device(h_eff_undesired, self.cdtype)
+            s = s + torch.matmul(hu, hu.mH)
+        return s
+
+    def compute_desired_signal_power(self, h_eff_desired, f):
+        """h_eff_desired [..., rxa, S], f [..., S, rxa] -> |f_s . h_s|^2 [..., S] (:656-675)"""
+        return torch.abs(torch.einsum("...mn,...nm->...m", f, h_eff_desired)) ** 2
+
+    def compute_total_power(self, h_eff_desired, h_eff_undesired, f):
+        """-> sum over all desired and undesired columns of |f_s . h_c|^2 [..., S] (:677-701)"""
+        h_eff = torch.cat([h_eff_desired, h_eff_undesired], dim=-1)
+        return torch.sum(torch.abs(torch.matmul(f, h_eff)) ** 2, dim=-1)
+
+    def compute_noise_power(self, no, f):
+        """no [..., rxa], f [..., S, rxa] -> sum_a |f_sa|^2 no_a [..., S] (:703-717)"""
+        no = torch.real(no) if no.dtype.is_complex else no
+        return torch.sum(torch.abs(f) ** 2 * no.unsqueeze(-2), dim=-1)
+
+    def compute_sinr(self, h_eff_desired, h_eff_undesired, no, f):
+        """-> sinr [B, T, Fe, rx, S] = signal / (max(total - signal, 0) + noise), 0 where that is 0 (:719-752)"""
+        signal = self.compute_desired_signal_power(h_eff_desired, f)
+        total = self.compute_total_power(h_eff_desired, h_eff_undesired, f)
+        interference = torch.clamp(total - signal, min=0)
+        den = interference + self.compute_noise_power(no, f)
+        sinr = torch.where(den == 0, torch.zeros_like(signal), signal / torch.where(den == 0, torch.ones_like(den), den))
+        return sinr.permute(0, 2, 3, 1, 4)
+
+    @abstractmethod
+    def call(self, h_eff, no, h_eff_hat=None):
+        pass
+
+
+class LMMSEPostEqualizationSINR(PostEqualizationSINR):
+    """SINR of every stream after LMMSE equalisation (ofdm/equalization.py:758-839), one fused launch.
+
+    ``call(h_eff, no, h_eff_hat=None, interference_whitening=True)``.  As in the reference, EVERYTHING is computed from
+    ``h_eff_hat`` when it is given - the combiner and the signal, interference and noise powers; the true ``h_eff`` is then
+    unused.  Up to 16 receive antennas and 16 streams per receiver; any number of interfering streams."""
+
+    def __init__(self, resource_grid, stream_management, precision=None, **kwargs):
+        super().__init__(resource_grid, stream_management, precision=precision, **kwargs)
+        self._dev = None
+
+    def _tables(self):
+        if self._dev is None:
+            sm = self._stream_management
+            total = sm.num_rx * sm.num_tx * sm.num_streams_per_tx
+            des = np.ascontiguousarray(sm.detection_desired_ind, np.int32).reshape(-1)
+            und = np.ascontiguousarray(sm.detection_undesired_ind, np.int32).reshape(-1)
+            s, u = sm.num_streams_per_rx, sm.num_interfering_streams_per_rx
+            if des.size != sm.num_rx * s or und.size != sm.num_rx * u:
+                raise ValueError("LMMSEPostEqualizationSINR: the StreamManagement does not give every receiver the same "
+                                 "number of desired and interfering streams")
+            for ind in (des, und):
+                if ind.size and (ind.min() < 0 or ind.max() >= total):
+                    raise ValueError("LMMSEPostEqualizationSINR: a detection index of the StreamManagement names a stream "
+                                     "that does not exist")
+            self._dev = (_ffi.to_device(des, torch.int32), _ffi.to_device(und, torch.int32) if und.size else None, s, u)
+        return self._dev
+
+    def _check(self, hs, ns, hhs=None):
+        sm, name = self._stream_management, "LMMSEPostEqualizationSINR"
+        if len(hs) != 7 or hs[1] != sm.num_rx or hs[3] != sm.num_tx or hs[4] != sm.num_streams_per_tx:
+            raise ValueError(f"{name}: h_eff must have shape [batch_size, {sm.num_rx}, num_rx_ant, {sm.num_tx}, "
+                             f"{sm.num_streams_per_tx}, num_ofdm_symbols, num_effective_subcarriers], got {hs}")
+        if hhs is not None and tuple(hhs) != tuple(hs):
+            raise ValueError(f"{name}: h_eff_hat must have the shape of h_eff {hs}, got {hhs}")
+        if hs[2] > 16 or sm.num_streams_per_rx > 16:
+            raise ValueError(f"{name}: supported up to 16 receive antennas and 16 streams per receiver (got {hs[2]} antennas, "
+                             f"{sm.num_streams_per_rx} streams)")
+        full = (hs[0], hs[1], hs[2], hs[5], hs[6])
+        if len(ns) > 5 or tuple(ns) != full[:len(ns)]:
+            raise ValueError(f"{name}: no must have shape {list(full)} or its first n dims, got {ns}")
+
+    def __call__(self, h_eff, no, h_eff_hat=None, interference_whitening=True, **kwargs):
+        from ..mimo.precoding import _shape
+        self._check(_shape(h_eff), _shape(no), None if h_eff_hat is None else _shape(h_eff_hat))
+        no = no.item() if isinstance(no, np.ndarray) and no.ndim == 0 else no     # not a 1-element device tensor
+        return super().__call__(h_eff, no, h_eff_hat=h_eff_hat, interference_whitening=interference_whitening, **kwargs)
+
+    def call(self, h_eff, no, h_eff_hat=None, interference_whitening=True):
+        from ..mimo.precoding import _shape, expand_alpha
+        sm = self._stream_management
+        hs = _shape(h_eff)
+        self._check(hs, _shape(no), None if h_eff_hat is None else _shape(h_eff_hat))
+        dbl = self.precision == "double"
+        cdt, rdt = (torch.complex128, torch.float64) if dbl else (torch.complex64, torch.float32)
+        h = _ffi.to_device(h_eff if h_eff_hat is None else h_eff_hat, cdt)
+        b, rx, rxa, ntx, k, t, fe = hs
+        n0, n = expand_alpha(no, (b, rx, rxa, t, fe), rdt)
+        des, und, s, u = self._tables()
+        sinr = torch.empty((b, t, fe, rx, s), dtype=rdt, device=h.device)
+        fn = _ffi.lib().samd_lmmse_post_eq_sinr_c128 if dbl else _ffi.lib().samd_lmmse_post_eq_sinr_c64
+        _ffi.check(fn(_ffi.ptr(h), _ffi.ptr(n), n0, _ffi.ptr(des), _ffi.ptr(und), int(bool(interference_whitening)), b, rx, rxa,
+                      ntx, k, t, fe, s, u, _ffi.ptr(sinr), _ffi.stream()), "LMMSEPostEqualizationSINR")
+        return sinr
