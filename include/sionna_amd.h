@@ -971,6 +971,45 @@ int samd_conv_bcjr_f64(const double* llr_ch, const double* llr_a, int64_t batch,
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Turbo codes (csrc/turbo.hip), float32 (_f32) and float64 (_f64, precision = "double").  Two rate-1/2 recursive
+ * systematic constituent codes: polys HOST array of the 2 generator polynomials as for samd_conv_*, the first the
+ * feedback polynomial, constraint_length 3..8.  T = k + (terminate ? constraint_length - 1 : 0) trellis steps per
+ * constituent code; n codeword bits after puncturing.  All index tables are DEVICE int32 arrays built by
+ * sionna_amd/phy/fec/turbo/utils.py (turbo_tables); entries are positions in [0, n) or -1 (nothing there).
+ *   samd_turbo_encode       TurboEncoder.call (fec/turbo/encoding.py:365-421) with _conv_enc (:235-289), _puncture_cw
+ *                           (:291-341) and TurboTermination.termbits_conv2turbo (fec/turbo/utils.py:156-230):
+ *                           u [batch,k] bits -> c [batch,n].  perm [k] the interleaver (encoder 1 reads u[perm[t]]),
+ *                           opos [2][T][2] the position of output bit j of step t of encoder e, zpos0 / zpos1 the
+ *                           positions of the zero padding of the termination (-1: none).
+ *   samd_turbo_bcjr         one half-iteration of TurboDecoder.call (fec/turbo/decoding.py:357-435): the BCJR pass of
+ *                           one constituent code (BCJRDecoder.call, fec/conv/decoding.py:700-943) on the channel values
+ *                           llr_ch[cw n + idx[t][j]] (idx [T][2]; replaces depuncture and _convenc_cws, :254-312) with
+ *                           the a priori values la_in [batch,T].  mode SAMD_TURBO_EXT1: dst [batch,T], dst[scat[t]] =
+ *                           clip((L - ch) - a) (:407-413); SAMD_TURBO_EXT2: dst[scat[t]] = clip((L - a) - ch)
+ *                           (:417-423); SAMD_TURBO_FINAL: dst [batch,k], dst[scat[t]] = L, or 0 < L with hard_out
+ *                           (:428-432).  scat [k]: the inverse interleaver for EXT1, the interleaver otherwise.
+ *                           dst must not be la_in.  algorithm SAMD_CONV_MAP / _LOG / _MAXLOG.
+ * samd_turbo_bcjr needs a device workspace of samd_turbo_workspace_bytes(constraint_length, T, batch, dbl) bytes (0:
+ * the alphas fit into LDS; then workspace may be NULL); SAMD_ERR_WORKSPACE when it is smaller.
+ * ---------------------------------------------------------------------------------- */
+#define SAMD_TURBO_EXT1 0
+#define SAMD_TURBO_EXT2 1
+#define SAMD_TURBO_FINAL 2
+int samd_turbo_encode_f32(const float* u, const int32_t* perm, const int32_t* opos, int64_t batch, int k, int n,
+                          const uint32_t* polys, int constraint_length, int terminate, int zpos0, int zpos1, float* c,
+                          void* stream);
+int samd_turbo_encode_f64(const double* u, const int32_t* perm, const int32_t* opos, int64_t batch, int k, int n,
+                          const uint32_t* polys, int constraint_length, int terminate, int zpos0, int zpos1, double* c,
+                          void* stream);
+size_t samd_turbo_workspace_bytes(int constraint_length, int num_syms, int64_t batch, int dbl);
+int samd_turbo_bcjr_f32(const float* llr_ch, const int32_t* idx, const float* la_in, const int32_t* scat, int64_t batch,
+                        int n, int k, const uint32_t* polys, int constraint_length, int terminate, int algorithm, int mode,
+                        int hard_out, float* dst, void* workspace, size_t workspace_bytes, void* stream);
+int samd_turbo_bcjr_f64(const double* llr_ch, const int32_t* idx, const double* la_in, const int32_t* scat, int64_t batch,
+                        int n, int k, const uint32_t* polys, int constraint_length, int terminate, int algorithm, int mode,
+                        int hard_out, double* dst, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Ordered-statistics decoding (csrc/osd.hip), float32 (_f32) and float64 (_f64, precision = "double").
  *   samd_osd_decode         OSDecoder.call (fec/linear/decoding.py:415-478) with _find_mrb (:318-402), _find_min_dist
  *                           (:272-316) and _get_dist (:237-270): llr [batch,n] -> out [batch,n] hard decisions of the

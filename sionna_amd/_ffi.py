@@ -76,6 +76,11 @@ _SIGNATURES = {
     "samd_conv_viterbi_f64": (_i32, [_vp, _i64, _i32, _vp] + [_i32] * 6 + [_vp, _vp, _sz, _vp]),
     "samd_conv_bcjr_f32": (_i32, [_vp, _vp, _i64, _i32, _vp] + [_i32] * 6 + [_vp, _vp, _sz, _vp]),
     "samd_conv_bcjr_f64": (_i32, [_vp, _vp, _i64, _i32, _vp] + [_i32] * 6 + [_vp, _vp, _sz, _vp]),
+    "samd_turbo_encode_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "samd_turbo_encode_f64": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "samd_turbo_workspace_bytes": (_sz, [_i32, _i32, _i64, _i32]),
+    "samd_turbo_bcjr_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp] + [_i32] * 5 + [_vp, _vp, _sz, _vp]),
+    "samd_turbo_bcjr_f64": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp] + [_i32] * 5 + [_vp, _vp, _sz, _vp]),
     "samd_osd_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64]),
     "samd_osd_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "samd_osd_decode_f64": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),

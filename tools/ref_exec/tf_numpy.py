@@ -588,7 +588,13 @@ def make_tf():
             return _t((lo + (hi - lo) * self._g.random([int(v) for v in np.atleast_1d(shape)])).astype(dtype))
         def normal(self, shape, mean=0.0, stddev=1.0, dtype=np.float32, **k):
             return _t((mean + stddev * self._g.normal(size=[int(v) for v in np.atleast_1d(shape)])).astype(dtype))
-    tf.random = types.SimpleNamespace(Generator=_Generator)
+    def _stateless_uniform(shape, seed, minval=0, maxval=1, dtype=np.float32, **k):
+        """tf.random.stateless_uniform stand-in: a function of the seed alone (NOT TensorFlow's stream)"""
+        g = np.random.default_rng([int(v) & 0xFFFFFFFF for v in np.asarray(seed).ravel()])
+        lo, hi = float(minval), float(maxval)
+        return _t((lo + (hi - lo) * g.random([int(v) for v in np.atleast_1d(shape)])).astype(dtype._np if isinstance(dtype, DType) else dtype))
+    tf.random = types.SimpleNamespace(Generator=_Generator, stateless_uniform=_stateless_uniform)
+    tf.assert_equal = tf.debugging.assert_equal
     tf.name_scope = lambda *a, **k: _NullCtx()
     class Variable(Tensor):
         """tf.Variable stand-in (an ndarray view; ``isinstance(x, tf.Variable)`` is False for plain tensors)."""
