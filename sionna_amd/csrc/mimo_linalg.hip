@@ -6,64 +6,15 @@
 // The receiver kernels (csrc/mimo.hip, csrc/f64.hip) carry this algebra fused and unrolled for their sizes; these entries
 // are the stand-alone forms for code that calls the helpers directly (precoders, custom equalisers): one lane per item,
 // run-time M, K <= 16, arrays in scratch, the formulas of the reference in its order of operations (Cholesky factor,
-// triangular solves).  complex64 and complex128 (precision = "double", block.py:25-52).  Held to oracle/linalg.py - NumPy in
+// triangular solves: csrc/cx_linalg.h).  complex64 and complex128 (precision = "double", block.py:25-52).  Held to oracle/linalg.py - NumPy in
 // complex128 - at 1e-4 relative in single (conditioning of the test matrices) and 1e-10 in double (tests/test_gpu_linalg.py).
 #include "common.h"
+#include "cx_linalg.h"
 
 namespace samd {
 namespace {
 
 constexpr int kD = 16;
-
-template <typename R> struct cx { R re, im; };
-template <typename R> __device__ __forceinline__ cx<R> C(R r, R i) { return cx<R>{r, i}; }
-template <typename R> __device__ __forceinline__ cx<R> operator+(cx<R> a, cx<R> b) { return C<R>(a.re + b.re, a.im + b.im); }
-template <typename R> __device__ __forceinline__ cx<R> operator-(cx<R> a, cx<R> b) { return C<R>(a.re - b.re, a.im - b.im); }
-template <typename R> __device__ __forceinline__ cx<R> operator*(cx<R> a, cx<R> b) {
-  return C<R>(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re);
-}
-template <typename R> __device__ __forceinline__ cx<R> mulcj(cx<R> a, cx<R> b) {      // a conj(b)
-  return C<R>(a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im);
-}
-template <typename R> __device__ __forceinline__ cx<R> cjm(cx<R> a, cx<R> b) {        // conj(a) b
-  return C<R>(a.re * b.re + a.im * b.im, a.re * b.im - a.im * b.re);
-}
-template <typename R> __device__ __forceinline__ cx<R> sc(cx<R> a, R t) { return C<R>(a.re * t, a.im * t); }
-
-// in-place lower Cholesky factor of the Hermitian n x n matrix a (row stride ld); the strict upper triangle is zeroed
-template <typename R> __device__ void chol(cx<R>* a, int n, int ld) {
-  for (int j = 0; j < n; ++j) {
-    R d = a[j * ld + j].re;
-    for (int q = 0; q < j; ++q) d -= a[j * ld + q].re * a[j * ld + q].re + a[j * ld + q].im * a[j * ld + q].im;
-    d = sqrt(d);
-    a[j * ld + j] = C<R>(d, R(0));
-    const R inv = R(1) / d;
-    for (int i = j + 1; i < n; ++i) {
-      cx<R> v = a[i * ld + j];
-      for (int q = 0; q < j; ++q) v = v - mulcj(a[i * ld + q], a[j * ld + q]);
-      a[i * ld + j] = sc(v, inv);
-    }
-    for (int i = 0; i < j; ++i) a[i * ld + j] = C<R>(R(0), R(0));
-  }
-}
-// x <- L^-1 x for `cols` right-hand sides x[row * ldx + col]
-template <typename R> __device__ void fwd(const cx<R>* l, int n, int ld, cx<R>* x, int ldx, int cols) {
-  for (int c = 0; c < cols; ++c)
-    for (int i = 0; i < n; ++i) {
-      cx<R> v = x[i * ldx + c];
-      for (int q = 0; q < i; ++q) v = v - l[i * ld + q] * x[q * ldx + c];
-      x[i * ldx + c] = sc(v, R(1) / l[i * ld + i].re);
-    }
-}
-// x <- L^-H x
-template <typename R> __device__ void bwd(const cx<R>* l, int n, int ld, cx<R>* x, int ldx, int cols) {
-  for (int c = 0; c < cols; ++c)
-    for (int i = n - 1; i >= 0; --i) {
-      cx<R> v = x[i * ldx + c];
-      for (int q = i + 1; q < n; ++q) v = v - cjm(l[q * ld + i], x[q * ldx + c]);
-      x[i * ldx + c] = sc(v, R(1) / l[i * ld + i].re);
-    }
-}
 
 template <typename R> __device__ __forceinline__ void load(const R* __restrict__ src, int64_t off, int count, cx<R>* dst) {
   for (int i = 0; i < count; ++i) dst[i] = C<R>(src[2 * (off + i)], src[2 * (off + i) + 1]);
@@ -77,9 +28,9 @@ template <typename R> __global__ __launch_bounds__(64) void inv_cholesky_kernel(
   if (it >= n) return;
   cx<R> A[kD * kD], X[kD * kD];
   load(a, it * M * M, M * M, A);
-  chol(A, M, M);
+  chol<R, 0>(A, M);
   for (int i = 0; i < M * M; ++i) X[i] = C<R>((i / M == i % M) ? R(1) : R(0), R(0));
-  fwd(A, M, M, X, M, M);
+  fwd<R, 0>(A, M, X, M, M);
   store(X, M * M, out, it * M * M);
 }
 
@@ -92,9 +43,9 @@ template <typename R> __global__ __launch_bounds__(64) void whiten_kernel(const 
   load(s, it * M * M, M * M, S);
   load(h, it * M * K, M * K, H);
   load(y, it * M, M, Y);
-  chol(S, M, M);
-  fwd(S, M, M, Y, 1, 1);
-  fwd(S, M, M, H, K, K);
+  chol<R, 0>(S, M);
+  fwd<R, 0>(S, M, Y, 1, 1);
+  fwd<R, 0>(S, M, H, K, K);
   store(Y, M, yw, it * M);
   store(H, M * K, hw, it * M * K);
 }
@@ -114,9 +65,9 @@ template <typename R> __global__ __launch_bounds__(64) void lmmse_matrix_kernel(
         for (int k = 0; k < K; ++k) v = v + mulcj(H[a * K + k], H[b * K + k]);
         A[a * M + b] = v;
       }
-    chol(A, M, M);
-    fwd(A, M, M, H, K, K);
-    bwd(A, M, M, H, K, K);                                           // (H H^H + S)^-1 H = G^H
+    chol<R, 0>(A, M);
+    fwd<R, 0>(A, M, H, K, K);
+    bwd<R, 0>(A, M, H, K, K);                                           // (H H^H + S)^-1 H = G^H
     for (int a = 0; a < K; ++a)
       for (int i = 0; i < M; ++i) G[a * M + i] = C<R>(H[i * K + a].re, -H[i * K + a].im);
   } else {
@@ -126,11 +77,11 @@ template <typename R> __global__ __launch_bounds__(64) void lmmse_matrix_kernel(
         for (int i = 0; i < M; ++i) v = v + cjm(H[i * K + a], H[i * K + b]);
         A[a * K + b] = v;
       }
-    chol(A, K, K);
+    chol<R, 0>(A, K);
     for (int a = 0; a < K; ++a)
       for (int i = 0; i < M; ++i) G[a * M + i] = C<R>(H[i * K + a].re, -H[i * K + a].im);
-    fwd(A, K, K, G, M, M);
-    bwd(A, K, K, G, M, M);
+    fwd<R, 0>(A, K, G, M, M);
+    bwd<R, 0>(A, K, G, M, M);
   }
   store(G, K * M, g, it * K * M);
 }

@@ -7,11 +7,11 @@
 // contraction (-ffp-contract=off), |z|^2 = re*re + im*im:
 //   Hd [RXA, S]  the receiver's desired columns, gathered through detection_desired_ind (flat over [rx, tx, stream]);
 //   V_ij = sum_u Hu_iu conj(Hu_ju) (j <= i) streamed over the U undesired columns (with interference whitening, else
-//          0), then V_ii.re += no_i;  V = L L^H (Cholesky-Banachiewicz);
+//          0), then V_ii.re += no_i;  V = L L^H (chol of csrc/cx_linalg.h, in the order stated there);
 //   Li = L^-1 by forward substitution of the identity: Li_ic = ((i == c) - sum_{c <= q < i} L_iq Li_qc) * (1 / L_ii);
 //   Hw = Li Hd:  Hw_is = sum_{q <= i} Li_iq Hd_qs;
 //   A_ab = (a == b) + sum_i conj(Hw_ia) Hw_ib (b <= a);  A = C C^H;  F = C^-H C^-1 Hw^H (forward, then backward
-//          substitution, each row times the reciprocal of C_ii);
+//          substitution in the order of cx_linalg.h, each row times the reciprocal of C_ii);
 //   signal_s = |sum_a F_sa Hw_as|^2;
 //   total_s  = sum_c |sum_a F_sa w_ac|^2 over the S desired and then the U undesired columns, each undesired column
 //          whitened on the fly (w = Li hu) whether or not it entered V, as the reference does;
@@ -20,57 +20,12 @@
 // (RXA, S) in (1,1) (2,1) (2,2) (4,2) (4,4) are compiled with constant sizes (arrays in registers, loops unrolled);
 // the rest of RXA <= 16, S <= 16 runs one run-time-size instantiation with its arrays in scratch.  U has no cap.
 #include "common.h"
+#include "cx_linalg.h"
 
 namespace samd {
 namespace {
 
 constexpr int kD = 16, kBlock = 128;
-
-template <typename R> struct cx { R re, im; };
-template <typename R> __device__ __forceinline__ cx<R> C(R r, R i) { return cx<R>{r, i}; }
-template <typename R> __device__ __forceinline__ cx<R> operator+(cx<R> a, cx<R> b) { return C<R>(a.re + b.re, a.im + b.im); }
-template <typename R> __device__ __forceinline__ cx<R> operator-(cx<R> a, cx<R> b) { return C<R>(a.re - b.re, a.im - b.im); }
-template <typename R> __device__ __forceinline__ cx<R> operator*(cx<R> a, cx<R> b) {
-  return C<R>(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re);
-}
-template <typename R> __device__ __forceinline__ cx<R> mulcj(cx<R> a, cx<R> b) {      // a conj(b)
-  return C<R>(a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im);
-}
-template <typename R> __device__ __forceinline__ cx<R> cjm(cx<R> a, cx<R> b) {        // conj(a) b
-  return C<R>(a.re * b.re + a.im * b.im, a.re * b.im - a.im * b.re);
-}
-template <typename R> __device__ __forceinline__ cx<R> sc(cx<R> a, R t) { return C<R>(a.re * t, a.im * t); }
-template <typename R> __device__ __forceinline__ R abs2(cx<R> a) { return a.re * a.re + a.im * a.im; }
-
-template <typename R> struct vec2;
-template <> struct vec2<float> { using type = float2; };
-template <> struct vec2<double> { using type = double2; };
-template <typename R> __device__ __forceinline__ cx<R> ld(const R* __restrict__ p, int64_t i) {
-  const typename vec2<R>::type v = reinterpret_cast<const typename vec2<R>::type*>(p)[i];
-  return C<R>(v.x, v.y);
-}
-
-// in-place lower Cholesky factor of the Hermitian n x n matrix a (row stride n; the lower triangle only)
-template <typename R, int NT> __device__ __forceinline__ void chol(cx<R>* a, int n_rt) {
-  const int n = NT ? NT : n_rt;
-  constexpr int U = NT ? 32 : 1;
-#pragma unroll U
-  for (int j = 0; j < n; ++j) {
-    R d = a[j * n + j].re;
-#pragma unroll U
-    for (int q = 0; q < j; ++q) d = d - abs2(a[j * n + q]);
-    d = sqrt(d);
-    a[j * n + j] = C<R>(d, R(0));
-    const R inv = R(1) / d;
-#pragma unroll U
-    for (int i = j + 1; i < n; ++i) {
-      cx<R> v = a[i * n + j];
-#pragma unroll U
-      for (int q = 0; q < j; ++q) v = v - mulcj(a[i * n + q], a[j * n + q]);
-      a[i * n + j] = sc(v, inv);
-    }
-  }
-}
 
 template <typename R> struct SinrArgs {
   const R* heff;       // [B, RX, RXA, TX, K, T, Fe] complex (the estimate when one is given)
@@ -157,6 +112,8 @@ template <typename R, int AT, int ST> __global__ __launch_bounds__(kBlock) void 
       A[a * S + c] = v;
     }
   chol<R, ST>(A, S);
+  // column i of Hw^H: the substitutions of cx_linalg.h written out, the forward one reading conj(Hd) in place of a
+  // copy (through fwd / bwd the run-time-size kernel stores and reloads every column first and runs 1.6 % longer)
 #pragma unroll UR
   for (int i = 0; i < RA; ++i) {
 #pragma unroll UR

@@ -12,13 +12,17 @@
 // One lane per item (an OFDM resource element (b, tx, t, f), f fastest, so that every load and store of a wave is
 // contiguous; or one matrix of the contiguous entry).  The order of operations is the float32 specification of
 // tests/precoding_f32.py, with every sum in ascending index order and no contraction (-ffp-contract=off):
-//   A_ij = sum_m H_im conj(H_jm) (j <= i), then A_ii.re += alpha;  Cholesky-Banachiewicz A = L L^H;
-//   X = L^-H L^-1 H (forward, then backward substitution, each row times the reciprocal of L_ii);
+//   A_ij = sum_m H_im conj(H_jm) (j <= i), then A_ii.re += alpha;
+//   A = L L^H and X = L^-H L^-1 H in the order stated in csrc/cx_linalg.h, column by column (both substitutions of a
+//   column before the next).  The complex type is that header's; the factor and the substitutions are written out here:
+//   called as chol / fwd / bwd, the same operations compile to other schedules that cost several constant-size kernels
+//   registers, scratch or occupancy.
 //   n_k = sqrt(sum_m (re^2 + im^2) of X_km);  G_mk = conj(X_km) / n_k as two divisions (0 where n_k == 0);
 //   x_precoded_m = sum_k G_mk x_k;  h_eff[r, a, k] = sum_m H_r[a, m] G_mk.
 // (K, M) pairs that occur in practice are compiled with constant sizes (arrays in registers, loops unrolled); the rest of
-// K <= 16, M <= 32 runs one run-time-size instantiation with its arrays in scratch, as csrc/mimo_linalg.hip does.
+// K <= 16, M <= 32 runs one run-time-size instantiation with its arrays in scratch and its loops rolled.
 #include "common.h"
+#include "cx_linalg.h"
 
 namespace samd {
 namespace {
@@ -26,36 +30,6 @@ namespace {
 constexpr int kKMax = 16, kMMax = 32, kBlock = 128;
 constexpr int kModeRzf = 0, kModeCbf = 1;
 constexpr int kModeEye = 2;                              // precoded channels only: G = I (K == M)
-
-template <typename R> struct cx { R re, im; };
-template <typename R> __device__ __forceinline__ cx<R> C(R r, R i) { return cx<R>{r, i}; }
-template <typename R> __device__ __forceinline__ cx<R> operator+(cx<R> a, cx<R> b) { return C<R>(a.re + b.re, a.im + b.im); }
-template <typename R> __device__ __forceinline__ cx<R> operator-(cx<R> a, cx<R> b) { return C<R>(a.re - b.re, a.im - b.im); }
-template <typename R> __device__ __forceinline__ cx<R> operator*(cx<R> a, cx<R> b) {
-  return C<R>(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re);
-}
-template <typename R> __device__ __forceinline__ cx<R> mulcj(cx<R> a, cx<R> b) {      // a conj(b)
-  return C<R>(a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im);
-}
-template <typename R> __device__ __forceinline__ cx<R> cjm(cx<R> a, cx<R> b) {        // conj(a) b
-  return C<R>(a.re * b.re + a.im * b.im, a.re * b.im - a.im * b.re);
-}
-template <typename R> __device__ __forceinline__ cx<R> sc(cx<R> a, R t) { return C<R>(a.re * t, a.im * t); }
-
-template <typename R> struct vec2;
-template <> struct vec2<float> { using type = float2; };
-template <> struct vec2<double> { using type = double2; };
-// element i of an interleaved complex array (one 8- / 16-byte access)
-template <typename R> __device__ __forceinline__ cx<R> ld(const R* __restrict__ p, int64_t i) {
-  const typename vec2<R>::type v = reinterpret_cast<const typename vec2<R>::type*>(p)[i];
-  return C<R>(v.x, v.y);
-}
-template <typename R> __device__ __forceinline__ void st(R* __restrict__ p, int64_t i, cx<R> v) {
-  typename vec2<R>::type w;
-  w.x = v.re;
-  w.y = v.im;
-  reinterpret_cast<typename vec2<R>::type*>(p)[i] = w;
-}
 
 // X [K, M] (row stride M) holds the channel H on entry.  On exit X[k * M + m] = G[m][k], the normalised precoding
 // matrix stored transposed.  A: K x K workspace.  KT / MT > 0: compile-time sizes.

@@ -33,6 +33,24 @@ def _zero(n):
     return C(np.zeros(n, F), np.zeros(n, F))
 
 
+def _forward(A, X, K, m):
+    """column m of X [K][M] <- L^-1 X for the factor ``cholesky`` left in A"""
+    for i in range(K):
+        v = X[i][m]
+        for q in range(i):
+            v = v - A[i][q] * X[q][m]
+        X[i][m] = v.scale(F(1) / A[i][i].re)
+
+
+def _backward(A, X, K, m):
+    """column m of X [K][M] <- L^-H X"""
+    for i in range(K - 1, -1, -1):
+        v = X[i][m]
+        for q in range(i + 1, K):
+            v = v - A[q][i].conj() * X[q][m]
+        X[i][m] = v.scale(F(1) / A[i][i].re)
+
+
 def _core(hf, al, mode):
     """hf [n, K, M] complex64, al [n] float32 -> Gt[k][m] = G_mk as lists of C over the n items."""
     n, K, M = hf.shape
@@ -49,16 +67,8 @@ def _core(hf, al, mode):
                 A[i][j] = v
         cholesky(A, K)
         for m in range(M):
-            for i in range(K):
-                v = X[i][m]
-                for q in range(i):
-                    v = v - A[i][q] * X[q][m]
-                X[i][m] = v.scale(F(1) / A[i][i].re)
-            for i in range(K - 1, -1, -1):
-                v = X[i][m]
-                for q in range(i + 1, K):
-                    v = v - A[q][i].conj() * X[q][m]
-                X[i][m] = v.scale(F(1) / A[i][i].re)
+            _forward(A, X, K, m)
+            _backward(A, X, K, m)
     for k in range(K):
         n2 = np.zeros(n, F)
         for m in range(M):
