@@ -158,7 +158,10 @@ JIT_DEV void jit_cn_store(U32 a0, unsigned off, const F32 (&c)[NCH], float* ws =
 // oc[h] = byte offset (constant part) of that VN's output element, JIT_NOOUT = not part of the output
 // xo[h] (FUSE): total of the fused degree-1 VN, for the generated code's output store after the last iteration.
 // PRUNE: lanes of pm[h] are check nodes the rate matching pruned (decoding.py:1344-1373) - they send 0 on every edge.
-template <int D, int NCH, bool FUSE, bool PRUNE = false, bool SP = false>
+// KEEP: bit i = the c2v of edge i is formed and stored.  All ones in every iteration but the last, where only the variable nodes
+// that are part of the output still read a c2v: the edges to the other columns drop out, and so does the next v2c of the fused
+// column (a last update is instantiated with FUSE only where xo is stored).
+template <int D, int NCH, bool FUSE, bool PRUNE = false, bool SP = false, unsigned KEEP = 0xFFFFFFFFu>
 JIT_DEV void jit_cn_update(F32 (&v)[D][NCH], U32 a0, const F32 (&lf)[NCH], float llr_max, float offset, F32 (&xo)[NCH],
                            const M64 (&pm)[NCH], float* ws = nullptr) {
   if (JIT_ABL & 1) {
@@ -224,6 +227,8 @@ JIT_DEV void jit_cn_update(F32 (&v)[D][NCH], U32 a0, const F32 (&lf)[NCH], float
   }
 #pragma unroll
   for (int i = 0; i < D; ++i) {
+    const bool keep = (KEEP >> i) & 1u;
+    if (!keep && !(FUSE && i == D - 1)) continue;
     F32 c2v[NCH];
 #pragma unroll
     for (int h = 0; h < NCH; ++h) {
@@ -233,10 +238,10 @@ JIT_DEV void jit_cn_update(F32 (&v)[D][NCH], U32 a0, const F32 (&lf)[NCH], float
       if (FUSE && i == D - 1) {
         const F32 x = c2v[h] + lf[h];                // (0 + c2v) + llr
         xo[h] = x;
-        c2v[h] = f_med3(x - c2v[h], -llr_max, llr_max);   // the slot now holds the next v2c
+        if (keep) c2v[h] = f_med3(x - c2v[h], -llr_max, llr_max);   // the slot now holds the next v2c
       }
     }
-    jit_cn_store<NCH, SP>(a0, (unsigned)i * JIT_Z4, c2v, ws);
+    if (keep) jit_cn_store<NCH, SP>(a0, (unsigned)i * JIT_Z4, c2v, ws);
   }
 }
 
@@ -507,6 +512,45 @@ JIT_DEV void jit_vnb_update(F32 (&c)[D][2], const U32 (&a)[D], const M64 (&sw)[D
     JIT_VN_EDGE(i, gm_st2(ws, a[i], 0u, o0, o1), lds_st2(a[i], 0u, o0, o1));
   }
   xo[0] = x0; xo[1] = x1;
+}
+
+// ---- the last iteration: nobody reads a v2c again, so a variable node forms its total - the same sum in the same order - and
+// nothing else: no clip(x - c), no node order -> slot order, no store
+template <int D>
+JIT_DEV void jit_vnb_total(F32 (&c)[D][2], const M64 (&sw)[D], const F32 (&l)[2], F32 (&xo)[2]) {
+  F32 x0 = 0.f, x1 = 0.f;
+  if (!(JIT_ABL & 2)) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) {                        // slot order -> node order
+      const F32 v0 = f_sel(sw[i], c[i][1], c[i][0]), v1 = f_sel(sw[i], c[i][0], c[i][1]);
+      f_pk_add(x0, x1, v0, v1);
+    }
+    f_pk_add(x0, x1, l[0], l[1]);
+  }
+  xo[0] = x0; xo[1] = x1;
+}
+template <int D, int NCH>
+JIT_DEV void jit_vn_total(F32 (&c)[D][NCH], const F32 (&l)[NCH], F32 (&x)[NCH]) {
+  if (JIT_ABL & 2) {
+#pragma unroll
+    for (int h = 0; h < NCH; ++h) x[h] = 0.f;
+    return;
+  }
+  if (NCH == 2) {
+    F32 x0 = 0.f, x1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < D; ++i) f_pk_add(x0, x1, c[i][0], c[i][NCH - 1]);
+    f_pk_add(x0, x1, l[0], l[NCH - 1]);
+    x[0] = x0; x[NCH - 1] = x1;
+  } else {
+#pragma unroll
+    for (int h = 0; h < NCH; ++h) {
+      x[h] = 0.f;
+#pragma unroll
+      for (int i = 0; i < D; ++i) x[h] = x[h] + c[i][h];
+      x[h] = x[h] + l[h];
+    }
+  }
 }
 
 template <int D, int NCH>

@@ -90,9 +90,12 @@ LDS_CYCLES = {"ds_read_b32": 2, "ds_read_b64": 2, "ds_read2_b32": 4, "ds_read2st
               "ds_write2_b64": 13, "ds_write_addtid_b32": 2, "ds_read_addtid_b32": 2, "ds_read2st64_b64": 8, "ds_write2st64_b64": 13}
 
 
-def per_iteration_stats(asm):
-    """The kernel is 16 wave programs, each [prologue + init | barrier | CN phase | barrier | VN phase | barrier]: instruction
-    classes and LDS-pipeline cycles of ONE iteration summed over the waves (what a CU executes per iteration and codeword)."""
+def per_iteration_stats(asm, waves=16):
+    """The kernel is `waves` wave programs.  With the last iteration inside the loop (boxplus-phi, the state variant) a program is
+    [prologue + init | barrier | CN phase | barrier | VN phase | barrier]; with the last iteration peeled (min-sum) it is
+    [prologue + init | barrier | CN phase | barrier | VN phase | barrier | last CN phase | barrier | last VN phase] and the last
+    VN phase, which no barrier follows, is counted with the next program's prologue under per_codeword.  Instruction classes and
+    LDS-pipeline cycles of ONE iteration summed over the waves (what a CU executes per iteration and codeword)."""
     body = asm[re.search(r"<samd_ldpc5g_jit\w*>:", asm).start():]
     segs = [[]]
     for line in body.splitlines():
@@ -102,12 +105,17 @@ def per_iteration_stats(asm):
         segs[-1].append(mm.group(1))
         if mm.group(1) == "s_barrier":
             segs.append([])
+    per = (len(segs) - 1) // waves                            # barriers of one wave program: 3, or 4 with a peeled last iteration
+    parts = [("cn_phase", segs[1::per]), ("vn_phase", segs[2::per]), ("per_codeword", segs[0:-1:per] + (segs[-1:] if per == 4 else []))]
+    if per == 4:
+        parts.insert(2, ("last_cn_phase", segs[3::per]))
     out = {}
-    for name, sel in (("cn_phase", segs[1::3]), ("vn_phase", segs[2::3]), ("per_codeword", segs[0:-1:3])):
+    for name, sel in parts:
         ops = [o for sg in sel for o in sg]
         unknown = sorted({o for o in ops if o.startswith("ds_") and o not in LDS_CYCLES})
         out[name] = {"valu": sum(o.startswith("v_") for o in ops), "salu": sum(o.startswith("s_") and o not in ("s_waitcnt", "s_nop", "s_barrier", "s_setprio") for o in ops),
                      "lds_insts": sum(o.startswith("ds_") for o in ops), "s_nop": ops.count("s_nop"),
+                     "cndmask": sum(o.startswith("v_cndmask") for o in ops),
                      "lds_pipe_cycles": sum(LDS_CYCLES.get(o, 0) for o in ops),
                      "lds_mix": dict(collections.Counter(o for o in ops if o.startswith("ds_"))),
                      "valu_per_wave": [sum(o.startswith("v_") for o in sg) for sg in sel]}
@@ -153,12 +161,12 @@ def main():
     print(f"  code bytes                   {4 * sum(len(l.split('//')[1].split(':')[1].split()) for l in body.splitlines() if '//' in l and ':' in l.split('//')[1])}")
     st = isa_stats(body)
     print("  instructions:", dict(st))
-    it = per_iteration_stats(asm)
+    it = per_iteration_stats(asm, int(src.split("// JIT_WAVES ")[1].split()[0]))
     import json
     json.dump(it, open(os.path.join(a.out, "per_iteration.json"), "w"), indent=1)
-    for ph in ("cn_phase", "vn_phase", "per_codeword"):
+    for ph in it:
         d = it[ph]
-        print(f"  {ph:13s} valu {d['valu']:5d}  salu {d['salu']:4d}  lds insts {d['lds_insts']:4d}  lds pipe cycles {d['lds_pipe_cycles']:5d}  {d['lds_mix']}")
+        print(f"  {ph:13s} valu {d['valu']:5d} (v_cndmask {d['cndmask']:4d})  salu {d['salu']:4d}  lds insts {d['lds_insts']:4d}  lds pipe cycles {d['lds_pipe_cycles']:5d}  {d['lds_mix']}")
     tot = it["cn_phase"]["lds_pipe_cycles"] + it["vn_phase"]["lds_pipe_cycles"]
     print(f"  per iteration and CU: {it['cn_phase']['valu'] + it['vn_phase']['valu']} VALU, {tot} LDS-pipeline cycles")
 
