@@ -1,1210 +1,23 @@
-// Specialised 5G LDPC flooding decoder: one straight-line program per wave, generated for ONE code and compiled at run
-// time (hipRTC, --offload-arch=gfx950).
-//
-// Replaces, for the codes of the grouped explicit-message kernel (csrc/ldpc5g_onchip_ms.inc: Z a multiple of 128, whole
-// base rows / columns, messages in LDS - BASELINE config C2), the same reference path: LDPC5GDecoder.call = rate
-// recovery + LDPCBPDecoder._bp_iter x num_iter + cn_update_(offset_)minsum + vn_update_sum + output mapping
-// (src/sionna/phy/fec/ldpc/decoding.py:1427-1536, 416-524, 681-953).
-//
-// Why: the generic kernel finds the work of a wave in lists - 103 k scalar instructions per C2 decode next to 163 k vector
-// ones (descriptor loads, switch trees, address arithmetic from table entries, priority bookkeeping), 40 % of the wave
-// cycles waiting.  The lists are a function of the code alone, so here the host writes them out as source:
-//   * every item is a call of its node update with CONSTANT block offsets - no descriptors, no dispatch, no loops;
-//   * the block positions of a wave's variable-node edges ((lane + shift) mod Z) are computed once per launch and stay in
-//     registers for all codewords and iterations (3 of the 7 vector operations per edge pair of the VN phase);
-//   * the channel LLRs a wave needs (its VN items' columns, the fused degree-1 columns of its CN items) stay in registers
-//     for the whole decode - no LLR array in LDS or L2, no per-codeword rate-recovery pass, no output pass: rate recovery
-//     is a constant offset in the load of the codeword, the marginals are written by the last VN / CN update.
-// Node arithmetic = csrc/jit/ldpc5g_jit_templates.h = ldpc5g_onchip_ms.inc operation for operation: the same bits.
-// The generic kernel stays the fallback (no libhiprtc, compile error, code outside the class, SAMD_LDPC_JIT=0).
-#include "ldpc5g_jit.h"
-
-#include <dlfcn.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <atomic>
-#include <cstdarg>
+// Specialised 5G LDPC flooding decoder, launch path and C ABI: which variant of a code's generated kernel a call needs, its
+// compiled code object and entry on the device, grid and workspace, the launch; the conversion of the state image.
+// The programs and why they exist: ldpc5g_jit_gen.cpp.  Their compilation and the code-object cache: ldpc5g_jit_rtc.cpp.
 #include <cstring>
-#include <functional>
-#include <map>
-#include <mutex>
-
 #include "ldpc5g.h"
-#include "jit_text.h"   // generated by the Makefile from csrc/jit/*.h: kJitOps, kJitTemplates
+#include "ldpc5g_jit_rtc.h"
 
 namespace samd {
-
-// class 1: every 64-lane chunk of a column is of ONE kind (information / filler / transmitted parity / punctured) and, with
-// the output interleaver, inside one of its rows: offsets are then constants + lane * stride
-static bool jit_class1(const samd_ldpc5g* h) {
-  if (!h || !h->jit_plan || h->jit_plan->general || !h->ms.g_ok) return false;
-  const int z = h->z;
-  if (z % 128 != 0 || h->k % 64 != 0 || h->n % 64 != 0) return false;
-  if (h->m_int > 0 && (h->n % h->m_int != 0 || (h->n / h->m_int) % 64 != 0)) return false;
-  if ((size_t)h->jit_plan->edges * z * 4 > 160 * 1024) return false;
-  return true;
-}
-
-// Any even lifting size: how many codewords a workgroup decodes side by side and on how many waves.  A lane owns two lifted
-// copies, so G codewords fill G Z / 2 lanes; the messages of a group (8 bytes per edge and lane; the lanes beyond G Z / 2 of
-// the last 64-lane chunk are switched off) must fit the workgroup's share of the CU's 160 KB.  Preferred: full chunks (no padding lanes), at least two items per wave and phase,
-// then as many codewords per CU as fit (C4's code, BG2 Z = 80: 6 codewords = 240 lanes = 4 chunks, 148 KB, one workgroup).
-bool jit_geometry(const samd_ldpc5g* h, bool phi, JitGeometry* out) {
-  if (!h || !h->jit_plan) return false;
-  const JitPlan& P = *h->jit_plan;
-  const int z = h->z;
-  if (z < 2 || P.edges <= 0 || P.ncu <= 0) return false;
-  if (h->m_int > 0 && h->n % h->m_int != 0) return false;
-  for (int r = 0; r < P.ncu; ++r)
-    if (P.row_deg[r] < 2 || P.row_deg[r] > 19) return false;
-  for (int c = 0; c < P.nbu; ++c)
-    if (P.col_edges[c].size() > 30) return false;
-  const size_t budget = 160 * 1024;
-  double best = -1.0;
-  JitGeometry g;
-  // two ways to fill an 8-byte slot: the copies (z, z + Z / 2) of one codeword (even Z; a rotation may swap the pair: four
-  // selections per edge pair in the variable-node phase) or copy z of two codewords (any Z, never swapped, an even number of
-  // codewords per workgroup).  The second wins a tie: fewer vector instructions for the same lanes and the same LDS.
-  for (int px = 0; px < 2; ++px) {
-    if (!px && (z & 1)) continue;
-    const int H = px ? z : z / 2;
-    for (int wgs : {1, 2, 4}) {
-      const int nw = 16 / wgs;
-      for (int G = 1; G <= 64; ++G) {
-        const int lanes = G * H, chunks = (lanes + 63) / 64;
-        const size_t lds = (size_t)P.edges * lanes * 8 + (phi ? 1024 : 0);   // (phi: the table of the logarithm, 512-byte aligned)
-        if (lds * wgs > budget || chunks > 16) break;
-        const double eff = (double)lanes / (64.0 * chunks);
-        const double fill = std::min(1.0, (double)(P.ncu * chunks) / (2.0 * nw));
-        // one workgroup of 16 waves per CU first: two of 8 only if that fills lanes or waves better
-        const double score = eff * fill + 1e-3 * std::min(1.0, (double)(G * (px ? 2 : 1) * wgs) / 64.0) - 2e-3 * (wgs - 1) + (px ? 5e-4 : 0.0);
-        if (score > best) {
-          best = score;
-          g.G = G; g.pairx = px; g.H = H; g.P = lanes; g.chunks = chunks; g.blk = 8 * lanes; g.nw = nw; g.wgs = wgs;
-        }
-      }
-    }
-  }
-  if (best < 0.0 && !phi && !(z & 1)) {
-    // nothing fits: one codeword per workgroup with the blocks of the LAST base rows in an L2 workspace row (the structure of
-    // ldpc5g_onchip_mss.hip on the generated kernel).  Up to 30 % of the edges (measured, profiles/r06u: 5 ... 28 % spilled run 1.8 - 2.0 x
-    // the generic engines, 33 % at Z = 192 rate 1/3 0.71 x); beyond that the generic engines keep the code.
-    const int H = z / 2, chunks = (H + 63) / 64;
-    const int e_max = (int)(budget / ((size_t)H * 8));
-    int r0 = P.ncu;
-    while (r0 > 0 && (int)(P.row_off[r0 - 1] / (4 * z)) + P.row_deg[r0 - 1] > e_max) --r0;     // rows < r0 stay in LDS
-    const int e_lds = r0 < P.ncu ? (int)(P.row_off[r0] / (4 * z)) : P.edges;
-    if (r0 >= 4 && r0 < P.ncu && (P.edges - e_lds) * 10 <= P.edges * 3 && chunks <= 16) {
-      best = 0.0;
-      g.G = 1; g.pairx = 0; g.H = H; g.P = H; g.chunks = chunks; g.blk = 8 * H; g.nw = 16; g.wgs = 1;
-      g.spill_row = r0; g.e_lds = e_lds; g.ws_bytes = (size_t)(P.edges - e_lds) * g.blk;
-    }
-  }
-  if (best < 0.0) return false;
-  if (g.spill_row < 0) g.e_lds = P.edges;
-  if (out) *out = g;
-  return true;
-}
-
-int jit_class(const samd_ldpc5g* h, bool phi) {
-  if (!h || !h->jit_plan) return 0;
-  if (jit_class1(h)) return 1;
-  return jit_geometry(h, phi, nullptr) ? 2 : 0;
-}
-
-bool jit_eligible(const samd_ldpc5g* h) { return jit_class(h, false) != 0; }
-
-// graph data of the generator for a code build_onchip_bp_tables left without a plan (any lifting size / pruning / k / n)
-void build_jit_plan_general(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row) {
-  if (h->jit_plan) return;
-  const int z = h->z, ncu = (h->n_cn + z - 1) / z, nbu = (h->n_vn + z - 1) / z;
-  JitPlan* plan = new JitPlan();
-  plan->general = 1;
-  plan->z = z; plan->ncu = ncu; plan->nbu = nbu;
-  plan->row_off.resize(ncu); plan->row_deg.resize(ncu); plan->fused_col.assign(ncu, -1);
-  plan->col_edges.resize(nbu); plan->col_fused.assign(nbu, 0);
-  int edges = 0;
-  for (int r = 0; r < ncu; ++r) {
-    const int d = (int)by_row[r].size();
-    plan->row_off[r] = edges * z * 4;                       // (edge index) x 4 Z, the convention of build_onchip_bp_tables
-    plan->row_deg[r] = d;
-    for (int i = 0; i < d; ++i) {
-      const int c = by_row[r][i].first, sft = by_row[r][i].second;
-      if (c >= nbu) { delete plan; return; }
-      plan->col_edges[c].push_back({(edges + i) * z * 4, 4 * sft});      // rows ascending
-    }
-    edges += d;
-  }
-  plan->edges = edges;
-  // rows whose last edge is the only edge of its column, shift 0 (extension part of the base graph): that degree-1 VN is
-  // updated inside the check-node update
-  for (int r = 0; r < ncu; ++r) {
-    const int d = (int)by_row[r].size();
-    if (d < 2) continue;
-    const int c = by_row[r][d - 1].first, sft = by_row[r][d - 1].second;
-    if (plan->col_edges[c].size() == 1 && sft == 0) { plan->fused_col[r] = c; plan->col_fused[c] = 1; }
-  }
-  if (h->n_cn % z) { plan->prune_row = ncu - 1; plan->prune_z0 = h->n_cn - (ncu - 1) * z; }
-  h->jit_plan = plan;
-}
-
-namespace {
-
-struct Src {
-  std::string s;
-  void f(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    const int n = vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (n > 0) s.append(buf, std::min((size_t)n, sizeof(buf) - 1));
-  }
-};
-
-// kind of the 64 VNs (column c, chunk qq): where their channel values come from and where their marginals go
-struct Chunk {
-  enum Kind { LOAD, ZERO, FILLER } kind = ZERO;
-  unsigned in_off = 0;      // byte offset (constant part) in the received row; lane part = lane4 * stride
-  unsigned out_off = 0xFFFFFFFFu;
-  bool out_strided = false; // lane part of the output offset: lane4 * stride (codeword output) or lane4 (information bits)
-};
-
-Chunk classify(const samd_ldpc5g* h, int c, int qq, int return_infobits) {
-  Chunk r;
-  const int z = h->z, v0 = c * z + 64 * qq, fill = h->k_ldpc - h->k;
-  int u;
-  if (v0 < h->k) u = v0;
-  else if (v0 < h->k_ldpc) { r.kind = Chunk::FILLER; return r; }       // logit -llr_max (decoding.py:1455-1463)
-  else u = v0 - fill;
-  if (return_infobits && v0 < h->k) r.out_off = 4u * (unsigned)v0;
-  const int t0 = u - 2 * z;
-  if (t0 < 0 || t0 >= h->n) return r;                                  // punctured: LLR 0
-  int o0 = t0;
-  if (h->m_int > 0) {                                                  // out_int_inv (encoding.py:238-244)
-    const int q = h->n / h->m_int;
-    o0 = (t0 / q) + (t0 % q) * h->m_int;
-  }
-  r.kind = Chunk::LOAD;
-  r.in_off = 4u * (unsigned)o0;
-  if (!return_infobits) { r.out_off = 4u * (unsigned)o0; r.out_strided = true; }
-  return r;
-}
-
-}  // namespace
-
-// The schedule of the specialised kernel.  The lists the generic kernel walks (JitPlan::cn / vn) were balanced for ITS
-// costs - ~40 scalar instructions of dispatch per item next to ~11 vector instructions per edge pair, so three small
-// rows weigh as much as a degree-19 row plus two small ones.  Straight-line code has no dispatch: an item costs what its
-// node update costs (check node pair item: 11 D + 22 vector instructions, + 6 with a fused degree-1 column; variable node
-// pair item: 4 D LDS + 4 D + 8 vector instructions), and the items are distributed by THAT (longest processing time
-// first; wave w runs on SIMD w % 4, so balanced waves are balanced SIMDs).  A wave's items run largest first and carry an
-// issue priority by the share of the phase's longest list still ahead (ldpc5g.h: item_priorities).
-namespace {
-struct Sched { std::vector<std::vector<JitItem>> cn, vn; };   // [wave], in issue order
-
-// What an item weighs in the assignment: slope x degree + ovh, a check-node item + fused with a fused degree-1 column.  These
-// weights order the latency chains of the waves and were tuned on hardware (profiles/r05j_jit_interleaved_sched_sweep.txt);
-// valu_*: the vector instructions a check-node item issues, the second cost of the per-SIMD levelling below.
-struct ItemCost { int cn_slope, cn_ovh, cn_fused, vn_slope, vn_ovh, valu_cn_slope, valu_cn_ovh, valu_cn_fused; };
-constexpr ItemCost kCostMinSum = {10, 60, 6, 8, 10, 27, 54, 22};
-// boxplus-phi: a check-node item is four phi evaluations per edge pair (~165 vector instructions), everything else is small
-// beside it
-constexpr ItemCost kCostPhi = {100, 100, 3, 8, 10, 330, 80, 20};
-constexpr int kValuVnSlope = 17, kValuVnOvh = 16;
-
-// simd_cost (round 6): after the per-wave assignment, items are exchanged between waves of
-// DIFFERENT SIMDs (wave w runs on SIMD w % 4) while that lowers the largest per-SIMD sum of a second cost - the vector
-// instructions an item issues (slope x degree + ovh) - without raising the longest wave list: the check-node phase is bound by
-// the vector pipe of its busiest SIMD (profiles/r06w), the first cost (tuned on hardware) orders the latency chains of the waves.
-void lpt_assign(std::vector<std::pair<int, JitItem>>& items, int nw, bool rotate, std::vector<std::vector<JitItem>>* out,
-                const std::function<int(const JitItem&)>& simd_cost = nullptr) {
-  std::stable_sort(items.begin(), items.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-  std::vector<std::vector<std::pair<int, JitItem>>> per(nw);
-  std::vector<long> load(nw, 0);
-  for (auto& it : items) {
-    int w = 0;
-    for (int q = 1; q < nw; ++q)
-      if (load[q] < load[w]) w = q;
-    per[w].push_back(it);
-    load[w] += it.first;
-  }
-  // local search behind the greedy pass: move an item off the longest list, or swap one of its items with a smaller one
-  // of another list, while that shortens the longest list
-  for (int round = 0; round < 64; ++round) {
-    const int wm = (int)(std::max_element(load.begin(), load.end()) - load.begin());
-    long best = load[wm];
-    int bi = -1, bw = -1, bj = -1;
-    for (size_t i = 0; i < per[wm].size(); ++i)
-      for (int w = 0; w < nw; ++w) {
-        if (w == wm) continue;
-        const long ci = per[wm][i].first;
-        const long m0 = std::max(load[wm] - ci, load[w] + ci);                 // move i to w
-        if (m0 < best) { best = m0; bi = (int)i; bw = w; bj = -1; }
-        for (size_t j = 0; j < per[w].size(); ++j) {                           // swap i with j of w
-          const long cj = per[w][j].first;
-          const long m1 = std::max(load[wm] - ci + cj, load[w] + ci - cj);
-          if (cj < ci && m1 < best) { best = m1; bi = (int)i; bw = w; bj = (int)j; }
-        }
-      }
-    if (bi < 0) break;
-    const auto a = per[wm][bi];
-    if (bj < 0) {
-      per[wm].erase(per[wm].begin() + bi);
-      per[bw].push_back(a);
-      load[wm] -= a.first; load[bw] += a.first;
-    } else {
-      const auto b = per[bw][bj];
-      per[wm][bi] = b; per[bw][bj] = a;
-      load[wm] += b.first - a.first; load[bw] += a.first - b.first;
-    }
-  }
-  if (simd_cost && nw >= 8 && nw % 4 == 0) {
-    auto simd_load = [&](int q) {
-      long t = 0;
-      for (int w = q; w < nw; w += 4)
-        for (auto& it : per[w]) t += simd_cost(it.second);
-      return t;
-    };
-    const long cap = *std::max_element(load.begin(), load.end());
-    for (int round = 0; round < 256; ++round) {
-      long sl[4];
-      for (int q = 0; q < 4; ++q) sl[q] = simd_load(q);
-      const int qm = (int)(std::max_element(sl, sl + 4) - sl);
-      long best = sl[qm];
-      int bw = -1, bi = -1, cw = -1, cj = -1;
-      for (int w = qm; w < nw; w += 4)
-        for (size_t i = 0; i < per[w].size(); ++i)
-          for (int v = 0; v < nw; ++v) {
-            if (v % 4 == qm) continue;
-            for (size_t j = 0; j < per[v].size(); ++j) {                           // swap item i of w (busiest SIMD) with item j of v
-              const long ai = simd_cost(per[w][i].second), aj = simd_cost(per[v][j].second);
-              if (aj >= ai) continue;
-              const long lw = load[w] - per[w][i].first + per[v][j].first, lv = load[v] + per[w][i].first - per[v][j].first;
-              if (lw > cap || lv > cap) continue;
-              const long m = std::max(sl[qm] - ai + aj, sl[v % 4] + ai - aj);
-              if (m < best) { best = m; bw = w; bi = (int)i; cw = v; cj = (int)j; }
-            }
-          }
-      if (bw < 0) break;
-      std::swap(per[bw][bi], per[cw][cj]);
-      load[bw] += per[bw][bi].first - per[cw][cj].first;
-      load[cw] += per[cw][cj].first - per[bw][bi].first;
-    }
-  }
-  for (int w = 0; w < nw; ++w)
-    std::stable_sort(per[w].begin(), per[w].end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-  const long longest = std::max<long>(1, *std::max_element(load.begin(), load.end()));
-  out->assign(nw, {});
-  for (int w = 0; w < nw; ++w) {
-    if (rotate && per[w].size() > 1) std::rotate(per[w].begin(), per[w].begin() + ((w >> 2) % per[w].size()), per[w].end());
-    long rem = load[w];
-    for (auto& it : per[w]) {
-      JitItem ji = it.second;
-      ji.prio = (int)std::max<long>(0, std::min<long>(3, (4 * rem + longest - 1) / longest - 1));
-      rem -= it.first;
-      (*out)[w].push_back(ji);
-    }
-  }
-}
-
-// The per-wave lists of the Z = 128 k class, by message layout and rule:
-//  * interleaved (Z = 128): every item a chunk pair - the high-degree columns too, a pair costs one block position per edge -
-//    distributed by the own assignment: 15.9 ms per 65536 C2 codewords against 16.7 ms on the generic kernel's lists, whose
-//    single-chunk items pay 4-byte accesses with two-way bank conflicts in this layout
-//    (profiles/r05j_jit_interleaved_sched_sweep.txt).  With the per-SIMD levelling the lists stay with their waves, largest item
-//    first: handing wave w the variable-node list of wave nw - 1 - w measured 1 - 2 % slower (profiles/r06zc ... r06ze), rotating
-//    a wave's order by its index on its SIMD 0.5 % (min-sum) and 3.2 % (boxplus-phi) slower (profiles/r06zo, r06zp);
-//  * chunk-planar (larger Z): the generic kernel's lists, tuned on hardware over rounds 2-3 - own assignments measured 4-7 % slower
-//    for every cost model tried (profiles/r05c_jit_sched_sweep.txt: an item's cost is its latency chain, not its instruction
-//    count) - with the variable-node lists handed out in reverse: the wave with the degree-19 row pair then does not also hold
-//    the 30 block positions of a degree-30 column.  boxplus-phi has no generic lists of its own weights and takes the own
-//    assignment here too, rotated and reversed as tuned in round 5; columns of degree > 12 and rows of degree > 12 (unrolled
-//    update: their values and sign words would not fit the registers) as two single-chunk items.
-Sched make_schedule(const samd_ldpc5g* h, bool phi) {
-  const JitPlan& P = *h->jit_plan;
-  const bool interleaved = h->z == 128;
-  Sched s;
-  if (!interleaved && !phi) {
-    s.cn = P.cn; s.vn = P.vn;
-    std::reverse(s.vn.begin(), s.vn.end());
-    return s;
-  }
-  const ItemCost& k = phi ? kCostPhi : kCostMinSum;
-  const int cn_pair_max = (phi && !interleaved) ? 12 : 32, vn_pair_max = interleaved ? 30 : 12;
-  const int nw = (int)P.cn.size();
-  const int chunks = h->z / 64;
-  std::vector<std::pair<int, JitItem>> ci, vi;
-  for (int r = 0; r < P.ncu; ++r)
-    for (int q = 0; q + 1 < chunks; q += 2) {
-      const int cost = k.cn_slope * P.row_deg[r] + k.cn_ovh + (P.fused_col[r] >= 0 ? k.cn_fused : 0);
-      if (P.row_deg[r] <= cn_pair_max) ci.push_back({cost, JitItem{r, q, 2, 0}});
-      else { ci.push_back({cost / 2, JitItem{r, q, 1, 0}}); ci.push_back({cost / 2, JitItem{r, q + 1, 1, 0}}); }
-    }
-  for (int c = 0; c < P.nbu; ++c) {
-    if (P.col_fused[c] || P.col_edges[c].empty()) continue;
-    const int d = (int)P.col_edges[c].size();
-    for (int q = 0; q + 1 < chunks; q += 2) {
-      if (d <= vn_pair_max) vi.push_back({k.vn_slope * d + k.vn_ovh, JitItem{c, q, 2, 0}});
-      else {                                                   // high-degree columns: one chunk per item (registers)
-        vi.push_back({k.vn_slope * d / 2 + k.vn_ovh, JitItem{c, q, 1, 0}});
-        vi.push_back({k.vn_slope * d / 2 + k.vn_ovh, JitItem{c, q + 1, 1, 0}});
-      }
-    }
-  }
-  const JitPlan* Pp = &P;
-  const ItemCost* kp = &k;
-  const std::function<int(const JitItem&)> ccost = [Pp, kp](const JitItem& it) {
-    return (kp->valu_cn_slope * Pp->row_deg[it.idx] + kp->valu_cn_ovh + (Pp->fused_col[it.idx] >= 0 ? kp->valu_cn_fused : 0)) * it.nch / 2;
-  };
-  const std::function<int(const JitItem&)> vcost = [Pp](const JitItem& it) {
-    return (kValuVnSlope * (int)Pp->col_edges[it.idx].size() + kValuVnOvh) * it.nch / 2;
-  };
-  lpt_assign(ci, nw, !interleaved, &s.cn, ccost);
-  lpt_assign(vi, nw, !interleaved, &s.vn, vcost);
-  if (!interleaved) std::reverse(s.vn.begin(), s.vn.end());
-  return s;
-}
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------ any even lifting size
-// The programs of jit_generate_source for the codes outside the Z = 128 k class: the same node updates on the same
-// interleaved layout, with the lane geometry of JitGeometry (a lane owns the copies (z, z + Z / 2) of one of G codewords),
-// rate recovery / output offsets per lane and the pruned tail of the last base row as a lane mask.
-// boxplus-phi: the 512-byte table of the logarithm sits at LDS address 0 and the messages behind it, so that an entry's address
-// is its offset alone (behind the messages it took one v_or_b32 per lookup to add the table's address)
-static constexpr unsigned kPhiTabBytes = 512u;
-
-// the defines of a boxplus-phi kernel; the table rows as one macro (the embedded text of csrc/phi_tab.inc, comment line dropped,
-// line continuations added)
-static void emit_phi_defines(Src& o) {
-  o.f("#define JIT_RULE_PHI 1\n#define JIT_PHI_TAB 0u\n#define JIT_PHI_TAB_ROWS \\\n");
-  std::string rows = kJitPhiTabRows;
-  const size_t pos = rows.find("*/");
-  if (pos != std::string::npos) rows = rows.substr(pos + 2);
-  for (char ch : rows) {
-    if (ch == '\n') o.s += " \\\n";
-    else o.s += ch;
-  }
-  o.s += "\n";
-}
-
-static std::string jit_generate_source_general(const samd_ldpc5g* h, int return_infobits, int rule, bool with_ops, JitVariant var) {
-  const int offset0 = rule == 1 ? 1 : 0;
-  const bool phi = rule == 2;
-  const JitPlan& P = *h->jit_plan;
-  JitGeometry g;
-  if (!jit_geometry(h, phi, &g)) return std::string();
-  const int z = h->z, H = g.H, nw = g.nw, chunks = g.chunks;
-  const ItemCost& k = phi ? kCostPhi : kCostMinSum;
-  // ---- schedule: every (row, chunk) / (column, chunk) is one item of two values per lane; longest processing time first.
-  // The lanes beyond G Z / 2 of the last chunk must do nothing.  Switching them off around every item (one divergent region
-  // each) cost 494 spilled registers at Z = 96 against 48 without the regions: the items of a partly filled last chunk go to
-  // waves of their own - about nw / chunks of them, the chunk's share of the work - whose whole program is ONE region.
-  const bool partial = (g.P % 64) != 0;
-  int nw_part = 0;
-  if (partial) nw_part = chunks == 1 ? nw : std::max(1, std::min(nw - 1, (nw + chunks / 2) / chunks));
-  const int nw_full = nw - nw_part;
-  std::vector<std::pair<int, JitItem>> ci[2], vi[2];
-  for (int r = 0; r < P.ncu; ++r)
-    for (int q = 0; q < chunks; ++q)
-      ci[partial && q == chunks - 1].push_back({k.cn_slope * P.row_deg[r] + k.cn_ovh + (P.fused_col[r] >= 0 ? k.cn_fused : 0), JitItem{r, q, 2, 0}});
-  for (int c = 0; c < P.nbu; ++c) {
-    if (P.col_fused[c] || P.col_edges[c].empty()) continue;
-    for (int q = 0; q < chunks; ++q)
-      vi[partial && q == chunks - 1].push_back({k.vn_slope * (int)P.col_edges[c].size() + k.vn_ovh, JitItem{c, q, 2, 0}});
-  }
-  Sched S;
-  {
-    Sched sa, sb;
-    // (a wave's order rotated by its index on its SIMD: the four waves of a SIMD start a phase on items of different size)
-    if (nw_full > 0) { lpt_assign(ci[0], nw_full, true, &sa.cn); lpt_assign(vi[0], nw_full, true, &sa.vn); }
-    if (nw_part > 0) { lpt_assign(ci[1], nw_part, true, &sb.cn); lpt_assign(vi[1], nw_part, true, &sb.vn); }
-    // the wave with the largest check-node items takes the smallest variable-node list of its set
-    std::reverse(sa.vn.begin(), sa.vn.end()); std::reverse(sb.vn.begin(), sb.vn.end());
-    S.cn = sa.cn; S.cn.insert(S.cn.end(), sb.cn.begin(), sb.cn.end());
-    S.vn = sa.vn; S.vn.insert(S.vn.end(), sb.vn.begin(), sb.vn.end());
-  }
-  auto edge_index = [&](int32_t first) { return (int)(first / (4 * z)); };
-  const bool spill = g.spill_row >= 0;
-  if (var.state && (spill || nw_full == 0)) return std::string();      // state variant: messages in LDS, at least one whole wave to move the image
-  const unsigned img_bytes = (unsigned)(g.e_lds * g.blk);
-  auto e_sp = [&](int e) { return e >= g.e_lds; };                                  // the edge's block lives in the workspace row
-  const unsigned msg0 = phi ? kPhiTabBytes : 0u;              // where the messages start in LDS
-  auto e_off = [&](int e) { return e >= g.e_lds ? (unsigned)((e - g.e_lds) * g.blk) : msg0 + (unsigned)(e * g.blk); };   // byte offset in LDS / in that row
-  const char* bar = spill ? "jit_barrier_g" : "jit_barrier";
-  Src o;
-  const bool px = g.pairx != 0;
-  const int cwg = px ? 2 * g.G : g.G;                          // codewords per workgroup
-  o.f("// JIT_WAVES %d\n// JIT_GROUP %d\n// JIT_WGS %d\n// JIT_WS_BYTES %zu\n#define JIT_NWAVES %d\n#define JIT_WS_FLOATS %zu\n", nw, cwg, g.wgs,
-      g.ws_bytes, nw, g.ws_bytes / 4);
-  if (spill)
-    o.f("// messages beyond LDS: base rows >= %d (%d of %d edges) in the workgroup's row of the workspace (L2)\n", g.spill_row,
-        P.edges - g.e_lds, P.edges);
-  o.f("// specialised 5G LDPC decoder (any lifting size): BG%d Z=%d k=%d n=%d m_int=%d pruned=%d return_infobits=%d %s\n", h->bg, z,
-      h->k, h->n, h->m_int, h->nb_pruned, return_infobits, phi ? "boxplus-phi" : offset0 ? "min-sum" : "offset-min-sum");
-  o.f("// geometry: %d codewords per workgroup (%s), %d lanes in %d chunks, %d bytes per edge block, %d workgroup(s) per CU\n", cwg,
-      px ? "a slot = copy z of two codewords" : "a slot = copies z, z + Z/2 of one codeword", g.P, chunks, g.blk, g.wgs);
-  o.f("#define JIT_OFFSET0 %d\n#define JIT_GENERAL 1\n#define JIT_LAYOUT_B 1\n", offset0 ? 1 : 0);
-  const unsigned lds_msg = ((msg0 + (unsigned)(g.e_lds * g.blk)) + 511u) & ~511u;
-  if (phi) emit_phi_defines(o);
-  if (var.state) o.f("// JIT_IMG_BYTES %u\n// JIT_IMG_MSG0 %u\n", (unsigned)(g.e_lds * g.blk), msg0);
-  const int stride = h->m_int > 0 ? h->m_int : 1;
-  const int nout = return_infobits ? h->k : h->n;
-  o.f("#define JIT_Z4 %uu\n#define JIT_Z %d\n#define JIT_H %d\n#define JIT_G %d\n#define JIT_P %d\n", (unsigned)g.blk, z, H, cwg, g.P);
-  o.f("#define JIT_K %d\n#define JIT_KLDPC %d\n#define JIT_FILLERS %d\n#define JIT_N %d\n#define JIT_NOUT %d\n#define JIT_M %uu\n"
-      "#define JIT_Q %d\n#define JIT_RIB %d\n#define JIT_LDS_FLOATS %u\n",
-      h->k, h->k_ldpc, h->k_ldpc - h->k, h->n, nout, (unsigned)stride, h->n / stride, return_infobits ? 1 : 0,
-      lds_msg / 4);
-  if (var.abl) o.f("#define JIT_ABL %d\n", var.abl);
-  if (with_ops) o.s += kJitOps;
-  o.s += kJitTemplates;
-  const char* args = "const float* llr_in, float* out, int batch, int num_iter, float llr_max, float offset, int hard_out, float* ws, "
-                     "const float* st_in, float* st_out";
-  for (int w = 0; w < nw; ++w) {
-    const auto& cn = S.cn[w];
-    const auto& vn = S.vn[w];
-    const bool wave_part = w >= nw_full;                     // all items of this wave lie in the partly filled last chunk
-    o.f("\nJIT_DEV void jit_wave_%d(%s) {\n", w, args);
-    o.f("  const U32 ln = jit_lane();\n  const U32 l8 = u_shl(ln, 3);\n  (void)offset; (void)hard_out; (void)st_in; (void)st_out;\n");
-    o.f("  float* wsw = ws + (size_t)JIT_BLOCK * JIT_WS_FLOATS;\n  (void)wsw;\n");
-    if (phi && w == 0) o.f("  jit_phi_stage(u_shl(ln, 2));\n");
-    // ---- lane geometry of the chunks this wave works on
-    std::vector<char> used(chunks, 0);
-    for (auto& it : cn) used[it.q] = 1;
-    for (auto& it : vn) used[it.q] = 1;
-    for (int q = 0; q < chunks; ++q)
-      if (used[q])
-        o.f("  const U32 p%d = ln + %uu; const M64 act%d = u_lt(p%d, %uu); const U32 g%d = u_div(p%d, %uu); const U32 z%d = p%d - g%d * %uu;\n",
-            q, 64u * q, q, q, (unsigned)g.P, q, q, (unsigned)H, q, q, q, (unsigned)H);
-    if (wave_part) o.f("  JIT_IF(act%d)\n", chunks - 1);
-    // ---- slots of the wave's variable-node edges, once per launch
-    for (size_t j = 0; j < vn.size(); ++j) {
-      const JitItem& it = vn[j];
-      const auto& ed = P.col_edges[it.idx];
-      for (size_t i = 0; i < ed.size(); ++i) {
-        const int sft = ed[i].second / 4, sh = sft % H, hi = (!px && sft >= H) ? 1 : 0;
-        if (px)
-          o.f("  const U32 va%zu_%zu = jit_vn_addr_g(p%d, z%d, %uu, %uu); const M64 vm%zu_%zu = jit_no_swap();\n", j, i, it.q, it.q,
-              (unsigned)sh, e_off(edge_index(ed[i].first)), j, i);
-        else
-        o.f("  const U32 va%zu_%zu = jit_vn_addr_g(p%d, z%d, %uu, %uu); const M64 vm%zu_%zu = jit_vn_swap_g(z%d, %uu, %s);\n", j, i,
-            it.q, it.q, (unsigned)sh, e_off(edge_index(ed[i].first)), j, i, it.q, (unsigned)sh, hi ? "true" : "false");
-      }
-      o.f("  // ^ column %d chunk %d\n", it.idx, it.q);
-    }
-    // ---- where the channel values come from / the marginals go: per lane, computed where they are used (u_here: kept in
-    // registers for the whole launch they are ~4 per item and the programs spill)
-    struct Need { std::string raw[2], in[2], out[2], cw[2]; int q; };
-    std::vector<Need> needs;
-    auto add_need = [&](const char* pre, size_t j, int c, int q) {
-      Need nd;
-      nd.q = q;
-      for (int hh = 0; hh < 2; ++hh) {
-        char a[160], b[320], r[32];
-        snprintf(r, sizeof(r), "r%s%zu_%d", pre, j, hh);
-        if (px) {                                               // the same node of codewords 2 g and 2 g + 1
-          snprintf(a, sizeof(a), "jit_in_off(u_here(z%d) + %uu, g%d + g%d + %uu, act%d)", q, (unsigned)(c * z), q, q, (unsigned)hh, q);
-          snprintf(b, sizeof(b), "jit_out_off(u_here(z%d) + %uu, g%d + g%d + %uu, act%d, %s)", q, (unsigned)(c * z), q, q, (unsigned)hh, q, a);
-        } else {
-          snprintf(a, sizeof(a), "jit_in_off(u_here(z%d) + %uu, g%d, act%d)", q, (unsigned)(c * z + hh * H), q, q);
-          snprintf(b, sizeof(b), "jit_out_off(u_here(z%d) + %uu, g%d, act%d, %s)", q, (unsigned)(c * z + hh * H), q, q, a);
-        }
-        nd.raw[hh] = r; nd.in[hh] = a; nd.out[hh] = b;
-        char cwn[48];                                           // which codeword of the group the value belongs to
-        if (px) snprintf(cwn, sizeof(cwn), "g%d + g%d + %uu", q, q, (unsigned)hh);
-        else snprintf(cwn, sizeof(cwn), "g%d", q);
-        nd.cw[hh] = cwn;
-      }
-      needs.push_back(nd);
-    };
-    for (size_t j = 0; j < vn.size(); ++j) add_need("v", j, vn[j].idx, vn[j].q);
-    for (size_t j = 0; j < cn.size(); ++j)
-      if (P.fused_col[cn[j].idx] >= 0) add_need("c", j, P.fused_col[cn[j].idx], cn[j].q);
-    auto raw_name = [&](const Need& nd, int hh) { return nd.raw[hh]; };
-    auto emit_raw_loads = [&]() {
-      for (auto& nd : needs)
-        for (int hh = 0; hh < 2; ++hh)
-          o.f("    F32 %s = jit_ld_raw(rows, %s, %s, rem, llr_max);\n", raw_name(nd, hh).c_str(), nd.in[hh].c_str(), nd.cw[hh].c_str());
-    };
-    o.f("  const int ngroups = (batch + %d) / %d;\n", cwg - 1, cwg);
-    const unsigned row_in = (unsigned)(cwg * h->n), row_out = (unsigned)(cwg * nout);
-    o.f("#pragma unroll 1\n  for (int b = JIT_BLOCK; b < ngroups; b += JIT_GRID) {\n");
-    o.f("    float* orow = out + (size_t)b * %uu;\n    const int rem = batch - b * %d;\n    (void)orow; (void)rem;\n", row_out, cwg);
-    // (requested here, not one group ahead: the values would wait in registers through a whole decode - C2 min-sum
-    // 15.58 -> 15.28 ms without that, 23 -> 4 spilled registers, profiles/r06zy)
-    o.f("    const float* rows = llr_in + (size_t)b * %uu;\n", row_in);
-    emit_raw_loads();
-    {
-      size_t ni = 0;
-      for (size_t j = 0; j < vn.size(); ++j, ++ni)
-        o.f("    const F32 lv%zu[2] = {jit_chan(%s, llr_max), jit_chan(%s, llr_max)};\n", j, raw_name(needs[ni], 0).c_str(),
-            raw_name(needs[ni], 1).c_str());
-      for (size_t j = 0; j < cn.size(); ++j) {
-        if (P.fused_col[cn[j].idx] < 0) continue;
-        o.f("    const F32 lc%zu[2] = {jit_chan(%s, llr_max), jit_chan(%s, llr_max)};\n", j, raw_name(needs[ni], 0).c_str(),
-            raw_name(needs[ni], 1).c_str());
-        ++ni;
-      }
-    }
-    auto emit_vb = [&](const char* indent, const char* name, size_t j) {
-      const int d = (int)P.col_edges[vn[j].idx].size();
-      o.f("%sconst U32 %s[%d] = {", indent, name, d);
-      for (int i = 0; i < d; ++i) o.f("%sva%zu_%d", i ? ", " : "", j, i);
-      o.f("}; const M64 %s_m[%d] = {", name, d);
-      for (int i = 0; i < d; ++i) o.f("%svm%zu_%d", i ? ", " : "", j, i);
-      o.f("};\n");
-    };
-    auto cn_base = [&](const JitItem& it) { return e_off(edge_index(P.row_off[it.idx])) + 512u * (unsigned)it.q; };
-    auto cn_sp = [&](const JitItem& it) { return spill && it.idx >= g.spill_row; };
-    auto vn_spm = [&](const JitItem& it) {                   // bit i: edge i of the column goes to a row in the workspace
-      unsigned mk = 0u;
-      const auto& ed = P.col_edges[it.idx];
-      for (size_t i = 0; i < ed.size(); ++i)
-        if (e_sp(edge_index(ed[i].first))) mk |= 1u << i;
-      return mk;
-    };
-    // ---- v2c of iteration 0 = channel LLR - or (state variant, round 6) the group's message image as a caller handed it in:
-    // the LDS image of the edge blocks of one workgroup pass, st_in[b][JIT_IMG bytes]; samd_ldpc5g_state_* convert it
-    if (var.state) {
-      if (!wave_part) o.f("    if (st_in) { JIT_KEEP_BRANCH(); jit_copy_g2l(st_in + (size_t)b * %uu, %uu, %uu, %d, %d); } else {\n", img_bytes / 4,
-                          msg0, img_bytes, w, nw_full);
-      else o.f("    if (st_in) { JIT_KEEP_BRANCH(); } else {\n");
-    }
-    for (size_t j = 0; j < vn.size(); ++j) {
-      o.f("    {\n");
-      emit_vb("      ", "vb", j);
-      o.f("      jit_vnb_init<%d, 0x%xu>(vb, vb_m, lv%zu, wsw);\n    }\n", (int)P.col_edges[vn[j].idx].size(), vn_spm(vn[j]), j);
-    }
-    for (size_t j = 0; j < cn.size(); ++j)
-      if (P.fused_col[cn[j].idx] >= 0)
-        o.f("    jit_cn_init_fused<%d, 2, %s>(jit_base(l8, %uu), lc%zu, wsw);\n", P.row_deg[cn[j].idx], cn_sp(cn[j]) ? "true" : "false",
-            cn_base(cn[j]), j);
-    if (var.state) o.f("    }\n");
-    o.f("    %s();\n", bar);
-    o.f("#pragma unroll 1\n    for (int it = 0; it < num_iter; ++it) {\n      const bool last = it == num_iter - 1;\n      (void)last;\n");
-    auto emit_out = [&](const Need& nd) {
-      o.f(" if (last) {");
-      for (int hh = 0; hh < 2; ++hh) o.f(" jit_st_out(orow, %s, %s, rem, xo[%d], llr_max, hard_out);", nd.out[hh].c_str(), nd.cw[hh].c_str(), hh);
-      o.f(" }");
-    };
-    // ---- CN phase: load - update - store, item by item.  boxplus-phi: the update with rolled loops, which reads its values
-    // itself, pass by pass
-    auto cn_load = [&](size_t j) {
-      const JitItem& it = cn[j];
-      if (phi) { o.f("      const U32 ca%zu = jit_base(l8, %uu);\n", j, cn_base(it)); return; }
-      o.f("      const U32 ca%zu = jit_base(l8, %uu); F32 cv%zu[%d][2]; jit_cn_load<%d, 2, %s>(cv%zu, ca%zu, wsw);\n", j, cn_base(it), j,
-          P.row_deg[it.idx], P.row_deg[it.idx], cn_sp(it) ? "true" : "false", j, j);
-    };
-    auto cn_update = [&](size_t j, const Need* nd) {
-      const JitItem& it = cn[j];
-      const int d = P.row_deg[it.idx];
-      const bool fuse = P.fused_col[it.idx] >= 0, prune = it.idx == P.prune_row;
-      o.f("      jit_setprio<%d>();\n", it.prio & 3);
-      o.f("      { F32 xo[2];");
-      if (prune && px) o.f(" const M64 pm[2] = {u_ge(z%d, %uu), u_ge(z%d, %uu)};", it.q, (unsigned)P.prune_z0, it.q, (unsigned)P.prune_z0);
-      else if (prune) o.f(" const M64 pm[2] = {u_ge(z%d, %uu), u_ge(z%d + %uu, %uu)};", it.q, (unsigned)P.prune_z0, it.q, (unsigned)H, (unsigned)P.prune_z0);
-      else o.f(" const M64 pm[2] = {};");
-      if (!fuse) o.f(" const F32 nolf[2] = {};");
-      char lf[24];
-      snprintf(lf, sizeof(lf), "lc%zu", j);
-      if (phi) o.f(" jit_cn_phi_rolled<%s, %s>(ca%zu, %d, %s, llr_max, xo, pm);", fuse ? "true" : "false", prune ? "true" : "false", j, d,
-                   fuse ? lf : "nolf");
-      else o.f(" jit_cn_update<%d, 2, %s, %s, %s>(cv%zu, ca%zu, %s, llr_max, offset, xo, pm, wsw);", d, fuse ? "true" : "false",
-               prune ? "true" : "false", cn_sp(it) ? "true" : "false", j, j, fuse ? lf : "nolf");
-      if (fuse) emit_out(*nd);
-      o.f(" }\n");
-    };
-    std::vector<const Need*> cn_need(cn.size(), nullptr);
-    {
-      size_t ni = vn.size();
-      for (size_t j = 0; j < cn.size(); ++j)
-        if (P.fused_col[cn[j].idx] >= 0) cn_need[j] = &needs[ni++];
-    }
-    o.f("      {\n");
-    for (size_t j = 0; j < cn.size(); ++j) {
-      cn_load(j);
-      cn_update(j, cn_need[j]);
-    }
-    o.f("      }\n      %s%s();\n", (var.abl & 4) ? "// " : "", bar);
-    // ---- VN phase
-    auto vn_load = [&](size_t j) {
-      const int d = (int)P.col_edges[vn[j].idx].size();
-      char nm[24];
-      snprintf(nm, sizeof(nm), "vb%zu", j);
-      emit_vb("      ", nm, j);
-      o.f("      F32 vc%zu[%d][2]; jit_vnb_load<%d, 0x%xu>(vc%zu, vb%zu, wsw);\n", j, d, d, vn_spm(vn[j]), j, j);
-    };
-    auto vn_update = [&](size_t j) {
-      const int d = (int)P.col_edges[vn[j].idx].size();
-      o.f("      jit_setprio<%d>();\n", vn[j].prio & 3);
-      o.f("      { F32 xo[2]; jit_vnb_update<%d, 0x%xu>(vc%zu, vb%zu, vb%zu_m, lv%zu, llr_max, xo, wsw);", d, vn_spm(vn[j]), j, j, j, j);
-      emit_out(needs[j]);
-      o.f(" }\n");
-    };
-    o.f("      {\n");
-    for (size_t j = 0; j < vn.size(); ++j) {
-      vn_load(j);
-      vn_update(j);
-    }
-    o.f("      }\n");
-    // the next group's first stores go to slots only this wave touches after the CN phase: no barrier behind the last VN phase
-    o.f("      %sif (!last) %s();\n    }\n", (var.abl & 4) ? "// " : "", bar);
-    if (var.state) {   // the image goes out after the last variable-node phase; barriers on both sides (the next group's first stores)
-      if (!wave_part) o.f("    if (st_out) { JIT_KEEP_BRANCH(); %s(); jit_copy_l2g(st_out + (size_t)b * %uu, %uu, %uu, %d, %d); %s(); }\n", bar,
-                          img_bytes / 4, msg0, img_bytes, w, nw_full, bar);
-      else o.f("    if (st_out) { JIT_KEEP_BRANCH(); %s(); %s(); }\n", bar, bar);
-    }
-    o.f("  }\n%s}\n", wave_part ? "  JIT_END\n" : "");
-  }
-  if (with_ops) {
-    // (a name per code and rule: kernel traces and counters of a process that decodes several codes stay apart)
-    char entry[96];
-    snprintf(entry, sizeof(entry), "samd_ldpc5g_jit_%s%s_bg%dz%dk%dn%d", phi ? "phi" : offset0 ? "ms" : "oms", var.state ? "_st" : "", h->bg, z,
-             h->k, h->n);
-    o.f("\n// JIT_ENTRY %s\nextern \"C\" __global__ __launch_bounds__(%d) void %s(%s) {\n", entry, 64 * nw, entry, args);
-    o.f("  __shared__ float jit_smem[JIT_LDS_FLOATS];\n");
-    o.f("  if ((unsigned)(unsigned long)(jit_lds_f32*)jit_smem != 0u) __builtin_trap();\n");
-    o.f("  switch (jit_wave()) {\n");
-    for (int w = 0; w < nw; ++w)
-      o.f("    case %d: jit_wave_%d(llr_in, out, batch, num_iter, llr_max, offset, hard_out, ws, st_in, st_out); break;\n", w, w);
-    o.f("    default: break;\n  }\n}\n");
-  }
-  return o.s;
-}
-
-std::string jit_generate_source(const samd_ldpc5g* h, int return_infobits, int rule, bool with_ops, JitVariant var) {
-  const int cls = jit_class(h, rule == 2);
-  if (cls == 0) return std::string();                         // (a code with min-sum kernels only, asked for boxplus-phi)
-  if (cls == 2) return jit_generate_source_general(h, return_infobits, rule, with_ops, var);
-  const int offset0 = rule == 1 ? 1 : 0;
-  const bool phi = rule == 2;
-  const JitPlan& P0 = *h->jit_plan;
-  const unsigned msg0 = phi ? kPhiTabBytes : 0u;              // where the messages start in LDS
-  const Sched S = make_schedule(h, phi);
-  struct PlanView {                                           // the plan's graph data + the schedule chosen above
-    const JitPlan& g;
-    const std::vector<std::vector<JitItem>>&cn, &vn;
-    const std::vector<int32_t>& row_off;
-    const std::vector<int>&row_deg, &fused_col;
-    const std::vector<std::vector<std::pair<int32_t, int32_t>>>& col_edges;
-    int edges;
-  } P{P0, S.cn, S.vn, P0.row_off, P0.row_deg, P0.fused_col, P0.col_edges, P0.edges};
-  const int z = h->z, z4 = 4 * z, nw = (int)P.cn.size();
-  const int stride = h->m_int > 0 ? h->m_int : 1;
-  Src o;
-  o.f("// JIT_WAVES %d\n#define JIT_NWAVES %d\n", nw, nw);
-  o.f("// specialised 5G LDPC decoder: BG%d Z=%d k=%d n=%d m_int=%d pruned=%d return_infobits=%d %s\n", h->bg, z, h->k, h->n,
-      h->m_int, h->nb_pruned, return_infobits, offset0 ? "min-sum" : "offset-min-sum");
-  o.f("#define JIT_OFFSET0 %d\n", offset0 ? 1 : 0);
-  if (phi) emit_phi_defines(o);
-  o.f("#define JIT_Z4 %uu\n#define JIT_N %d\n#define JIT_NOUT %d\n#define JIT_M %uu\n#define JIT_LDS_FLOATS %d\n", (unsigned)z4,
-      h->n, return_infobits ? h->k : h->n, (unsigned)stride, P.edges * z + (phi ? 128 : 0));
-  // message layout: the two chunks of an edge block interleaved exactly at Z = 128 (jit/ldpc5g_jit_templates.h: JIT_LAYOUT_B);
-  // larger Z of the class is chunk-planar
-  const bool lb = z == 128;
-  if (lb) o.f("#define JIT_LAYOUT_B 1\n");
-  if (var.abl) o.f("#define JIT_ABL %d\n", var.abl);
-  const unsigned img_bytes = (unsigned)(P.edges * z4);
-  if (var.state) o.f("// JIT_IMG_BYTES %u\n// JIT_IMG_MSG0 %u\n// state=1\n", img_bytes, msg0);
-  if (with_ops) o.s += kJitOps;
-  o.s += kJitTemplates;
-  const char* args = "const float* llr_in, float* out, int batch, int num_iter, float llr_max, float offset, int hard_out, float* ws, "
-                     "const float* st_in, float* st_out";
-  // min-sum / offset-min-sum without state: the last iteration does only what the outputs need.  edge_col: column of an edge block;
-  // col_last: the column has an item in the last variable-node phase (not fused, some chunk of it is part of the output)
-  const bool lean_last = !phi && !var.state;
-  std::vector<int> edge_col(P.edges, 0);
-  std::vector<char> col_last(P0.nbu, 0);
-  for (int c = 0; c < P0.nbu; ++c) {
-    for (auto& ed : P.col_edges[c]) edge_col[ed.first / z4] = c;
-    if (P0.col_fused[c]) continue;
-    for (int qq = 0; qq < z / 64; ++qq)
-      if (classify(h, c, qq, return_infobits).out_off != 0xFFFFFFFFu) col_last[c] = 1;
-  }
-  for (int w = 0; w < nw; ++w) {
-    const auto& cn = P.cn[w];
-    const auto& vn = P.vn[w];
-    o.f("\nJIT_DEV void jit_wave_%d(%s) {\n", w, args);
-    o.f("  const U32 l4 = jit_lane4();\n  const U32 l4m = l4 * JIT_M;\n  (void)l4m; (void)offset; (void)ws; (void)st_in; (void)st_out;\n");
-    if (lb) o.f("  const U32 l8 = l4 + l4;\n  (void)l8;\n");
-    if (phi && w == 0) o.f("  jit_phi_stage(l4);\n");
-    const char* lrow = lb ? "l8" : "l4";                      // lane part of a check-node slot address
-    // ---- block positions of the wave's variable-node edges: once per launch
-    for (size_t j = 0; j < vn.size(); ++j) {
-      const JitItem& it = vn[j];
-      const auto& ed = P.col_edges[it.idx];
-      const int d = (int)ed.size();
-      if (lb && it.nch == 2) {
-        // interleaved layout, pair item: slot (lane - shift) mod 64 of the edge's block, and the lanes whose own pair is swapped
-        for (int i = 0; i < d; ++i) {
-          const int s4 = ed[i].second % z4;                                  // 4 shift
-          const int k8 = (512 - (2 * s4) % 512) % 512, kb = (512 - s4) % 512;
-          if (var.abl & 16)   // development ablation: no lane ever swapped (WRONG results; the time without the four selections per edge pair)
-            o.f("  const U32 va%zu_0_%d = jit_vn_addr(l8, %uu, %uu); const M64 vm%zu_%d = u_testbit(l4 & 0u, 256u);\n", j, i, (unsigned)k8,
-                msg0 + (unsigned)ed[i].first, j, i);
-          else
-          o.f("  const U32 va%zu_0_%d = jit_vn_addr(l8, %uu, %uu); const M64 vm%zu_%d = u_testbit(l4 + %uu, 256u);\n", j, i, (unsigned)k8,
-              msg0 + (unsigned)ed[i].first, j, i, (unsigned)kb);
-        }
-      } else if (lb) {
-        for (int i = 0; i < d; ++i) {
-          const int kk = (((256 * it.q - ed[i].second) % z4) + z4) % z4;
-          o.f("  const U32 va%zu_0_%d = jit_vn_addr_b1(l4, %uu, %uu);\n", j, i, (unsigned)kk, msg0 + (unsigned)ed[i].first);
-        }
-      } else
-      for (int hh = 0; hh < it.nch; ++hh)
-        for (int i = 0; i < d; ++i) {
-          const int kk = (((256 * (it.q + hh) - ed[i].second) % z4) + z4) % z4;
-          o.f("  const U32 va%zu_%d_%d = jit_vn_addr(l4, %uu, %uu);\n", j, hh, i, (unsigned)kk, msg0 + (unsigned)ed[i].first);
-        }
-      o.f("  // ^ column %d chunk %d\n", it.idx, it.q);
-    }
-    // ---- channel values: where each chunk of the wave's columns comes from
-    struct Need { std::string name; Chunk ch; };
-    std::vector<Need> needs;   // lv<j>[h] for VN items, lc<j>[h] for fused CN items
-    auto add_need = [&](const char* pre, size_t j, int hh, int c, int qq) {
-      char nm[32];
-      snprintf(nm, sizeof(nm), "%s%zu_%d", pre, j, hh);
-      needs.push_back({nm, classify(h, c, qq, return_infobits)});
-    };
-    for (size_t j = 0; j < vn.size(); ++j)
-      for (int hh = 0; hh < vn[j].nch; ++hh) add_need("rv", j, hh, vn[j].idx, vn[j].q + hh);
-    for (size_t j = 0; j < cn.size(); ++j)
-      if (P.fused_col[cn[j].idx] >= 0)
-        for (int hh = 0; hh < cn[j].nch; ++hh) add_need("rc", j, hh, P.fused_col[cn[j].idx], cn[j].q + hh);
-    o.f("#pragma unroll 1\n  for (int b = JIT_BLOCK; b < batch; b += JIT_GRID) {\n");
-    o.f("    float* orow = out + (size_t)b * JIT_NOUT;\n    (void)orow;\n");
-    // (requested here, not one codeword ahead: the values would wait in ~40 registers through a whole decode - C2 min-sum
-    // 15.58 -> 15.28 ms without that, 23 -> 4 spilled registers, boxplus-phi unchanged, profiles/r06zy)
-    o.f("    const float* row = llr_in + (size_t)b * JIT_N;\n");
-    for (auto& nd : needs)
-      if (nd.ch.kind == Chunk::LOAD) o.f("    F32 %s = g_ld(row, l4m, %uu);\n", nd.name.c_str(), nd.ch.in_off);
-    // channel LLRs (decoding.py:552-565 + rate recovery 1438-1475)
-    auto chan_expr = [&](const Need& nd) {
-      if (nd.ch.kind == Chunk::LOAD) return "jit_chan(" + nd.name + ", llr_max)";
-      if (nd.ch.kind == Chunk::FILLER) return std::string("jit_chan(jit_bcast(-llr_max), llr_max)");
-      return std::string("jit_chan(jit_bcast(0.f), llr_max)");
-    };
-    {
-      size_t ni = 0;
-      for (size_t j = 0; j < vn.size(); ++j) {
-        o.f("    const F32 lv%zu[%d] = {", j, vn[j].nch);
-        for (int hh = 0; hh < vn[j].nch; ++hh, ++ni) o.f("%s%s", hh ? ", " : "", chan_expr(needs[ni]).c_str());
-        o.f("};\n");
-      }
-      for (size_t j = 0; j < cn.size(); ++j) {
-        if (P.fused_col[cn[j].idx] < 0) continue;
-        o.f("    const F32 lc%zu[%d] = {", j, cn[j].nch);
-        for (int hh = 0; hh < cn[j].nch; ++hh, ++ni) o.f("%s%s", hh ? ", " : "", chan_expr(needs[ni]).c_str());
-        o.f("};\n");
-      }
-    }
-    // ---- v2c of iteration 0 = channel LLR
-    // the positions an item uses: the launch-long registers
-    auto emit_vb = [&](const char* indent, const char* name, size_t j) {
-      const JitItem& it = vn[j];
-      const int d = (int)P.col_edges[it.idx].size();
-      if (lb && it.nch == 2) {
-        o.f("%sconst U32 %s[%d] = {", indent, name, d);
-        for (int i = 0; i < d; ++i) o.f("%sva%zu_0_%d", i ? ", " : "", j, i);
-        o.f("}; const M64 %s_m[%d] = {", name, d);
-        for (int i = 0; i < d; ++i) o.f("%svm%zu_%d", i ? ", " : "", j, i);
-        o.f("};\n");
-        return;
-      }
-      o.f("%sconst U32 %s[%d][%d] = {", indent, name, d, it.nch);
-      for (int i = 0; i < d; ++i) {
-        o.f("%s{", i ? ", " : "");
-        for (int hh = 0; hh < it.nch; ++hh) o.f("%sva%zu_%d_%d", hh ? ", " : "", j, hh, i);
-        o.f("}");
-      }
-      o.f("};\n");
-    };
-    if (var.state)   // (state variant, round 6: the codeword's message image as a caller handed it in instead of the channel values)
-      o.f("    if (st_in) { JIT_KEEP_BRANCH(); jit_copy_g2l(st_in + (size_t)b * %uu, %uu, %uu, %d, %d); } else {\n", img_bytes / 4, msg0,
-          img_bytes, w, nw);
-    for (size_t j = 0; j < vn.size(); ++j) {
-      const int d = (int)P.col_edges[vn[j].idx].size();
-      o.f("    {\n");
-      emit_vb("      ", "vb", j);
-      if (lb && vn[j].nch == 2) o.f("      jit_vnb_init<%d>(vb, vb_m, lv%zu);\n    }\n", d, j);
-      else o.f("      jit_vn_init<%d, %d>(vb, lv%zu);\n    }\n", d, vn[j].nch, j);
-    }
-    auto cn_base = [&](const JitItem& it) { return msg0 + (unsigned)(P.row_off[it.idx] + (lb ? 4 : 256) * it.q); };
-    for (size_t j = 0; j < cn.size(); ++j)
-      if (P.fused_col[cn[j].idx] >= 0)
-        o.f("    jit_cn_init_fused<%d, %d>(jit_base(%s, %uu), lc%zu);\n", P.row_deg[cn[j].idx], cn[j].nch, lrow, cn_base(cn[j]), j);
-    if (var.state) o.f("    }\n");
-    o.f("    jit_barrier();\n");
-    // ---- CN phase: load - update - store, item by item.  boxplus-phi pair items of the interleaved layout: the update with rolled
-    // loops, which reads its values itself (the chunk-planar class keeps the unrolled update)
-    auto is_rolled = [&](const JitItem& it) { return phi && lb && it.nch == 2; };
-    auto cn_load = [&](size_t j) {
-      const JitItem& it = cn[j];
-      if (is_rolled(it)) { o.f("      const U32 ca%zu = jit_base(%s, %uu);\n", j, lrow, cn_base(it)); return; }
-      o.f("      const U32 ca%zu = jit_base(%s, %uu); F32 cv%zu[%d][%d]; jit_cn_load<%d, %d>(cv%zu, ca%zu);\n", j, lrow, cn_base(it), j,
-          P.row_deg[it.idx], it.nch, P.row_deg[it.idx], it.nch, j, j);
-    };
-    auto out_offs = [&](int c, const JitItem& it, unsigned* oc, bool* strided) {
-      oc[0] = oc[1] = 0xFFFFFFFFu;
-      *strided = false;
-      for (int hh = 0; hh < it.nch; ++hh) {
-        const Chunk ch = classify(h, c, it.q + hh, return_infobits);
-        oc[hh] = ch.out_off;
-        if (ch.out_off != 0xFFFFFFFFu) *strided = ch.out_strided;
-      }
-    };
-    // the totals a node update returns go out after the last iteration (decoding.py:620-626): constant offsets per chunk
-    auto has_out = [&](const unsigned* oc, int nch) { return oc[0] != 0xFFFFFFFFu || (nch == 2 && oc[1] != 0xFFFFFFFFu); };
-    auto emit_out = [&](const char* xname, const unsigned* oc, bool strided, int nch, bool always) {
-      if (!has_out(oc, nch)) return;
-      o.f(always ? "      {" : "      if (last) {");
-      for (int hh = 0; hh < nch; ++hh)
-        if (oc[hh] != 0xFFFFFFFFu)
-          o.f(" g_st(orow, u_here(%s), 0x%xu, jit_outval(%s[%d], llr_max, hard_out));", strided ? "l4m" : "l4", oc[hh], xname, hh);
-      o.f(" }\n");
-    };
-    // Phase: BOTH = the body of a loop whose trips include the last one (outputs behind `if (last)`), INNER = a trip that is never
-    // the last (no outputs), LAST = the peeled last trip: only what the outputs need
-    enum Phase { BOTH, INNER, LAST };
-    auto cn_update = [&](size_t j, Phase ph) {
-      const JitItem& it = cn[j];
-      const int fc = P.fused_col[it.idx], d = P.row_deg[it.idx];
-      unsigned oc[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-      bool strided = false;
-      if (fc >= 0) out_offs(fc, it, oc, &strided);
-      o.f("      jit_setprio<%d>();\n", it.prio & 3);
-      o.f("      { F32 xo[%d]; const M64 nopm[%d] = {};", it.nch, it.nch);
-      if (is_rolled(it)) {
-        if (fc >= 0) o.f(" jit_cn_phi_rolled<true, false>(ca%zu, %d, lc%zu, llr_max, xo, nopm);\n", j, d, j);
-        else o.f(" const F32 nolf[2] = {}; jit_cn_phi_rolled<false, false>(ca%zu, %d, nolf, llr_max, xo, nopm);\n", j, d);
-      } else if (phi) {
-        if (fc >= 0) o.f(" jit_cn_update_phi<%d, %d, true>(cv%zu, ca%zu, lc%zu, llr_max, xo, nopm);\n", d, it.nch, j, j, j);
-        else o.f(" const F32 nolf[%d] = {}; jit_cn_update_phi<%d, %d, false>(cv%zu, ca%zu, nolf, llr_max, xo, nopm);\n", it.nch, d, it.nch, j, j);
-      } else if (ph == LAST) {
-        // c2v only for the edges whose column still has an item in the last variable-node phase; the fused column's total only
-        // where it is stored, its next v2c never
-        unsigned keep = 0u;
-        for (int i = 0; i < d; ++i)
-          if (col_last[edge_col[P.row_off[it.idx] / z4 + i]]) keep |= 1u << i;
-        const bool fuse = fc >= 0 && has_out(oc, it.nch);
-        if (fuse) o.f(" jit_cn_update<%d, %d, true, false, false, 0x%xu>(cv%zu, ca%zu, lc%zu, llr_max, offset, xo, nopm);\n", d, it.nch, keep, j, j, j);
-        else o.f(" const F32 nolf[%d] = {}; jit_cn_update<%d, %d, false, false, false, 0x%xu>(cv%zu, ca%zu, nolf, llr_max, offset, xo, nopm);\n",
-                 it.nch, d, it.nch, keep, j, j);
-      } else {
-        if (fc >= 0) o.f(" jit_cn_update<%d, %d, true>(cv%zu, ca%zu, lc%zu, llr_max, offset, xo, nopm);\n", d, it.nch, j, j, j);
-        else o.f(" const F32 nolf[%d] = {}; jit_cn_update<%d, %d, false>(cv%zu, ca%zu, nolf, llr_max, offset, xo, nopm);\n", it.nch, d, it.nch, j, j);
-      }
-      if (fc >= 0 && ph != INNER) emit_out("xo", oc, strided, it.nch, ph == LAST);
-      o.f("      }\n");
-    };
-    // ---- VN phase
-    auto vn_load = [&](size_t j) {
-      const JitItem& it = vn[j];
-      const int d = (int)P.col_edges[it.idx].size();
-      char nm[24];
-      snprintf(nm, sizeof(nm), "vb%zu", j);
-      emit_vb("      ", nm, j);
-      if (lb && it.nch == 2) o.f("      F32 vc%zu[%d][2]; jit_vnb_load<%d>(vc%zu, vb%zu);\n", j, d, d, j, j);
-      else o.f("      F32 vc%zu[%d][%d]; jit_vn_load<%d, %d>(vc%zu, vb%zu);\n", j, d, it.nch, d, it.nch, j, j);
-    };
-    auto vn_update = [&](size_t j, Phase ph) {
-      const JitItem& it = vn[j];
-      const int d = (int)P.col_edges[it.idx].size();
-      unsigned oc[2];
-      bool strided;
-      out_offs(it.idx, it, oc, &strided);
-      o.f("      jit_setprio<%d>();\n", it.prio & 3);
-      o.f("      { F32 xo[%d];", it.nch);
-      if (ph == LAST) {
-        if (lb && it.nch == 2) o.f(" jit_vnb_total<%d>(vc%zu, vb%zu_m, lv%zu, xo);\n", d, j, j, j);
-        else o.f(" jit_vn_total<%d, %d>(vc%zu, lv%zu, xo);\n", d, it.nch, j, j);
-      } else {
-        if (lb && it.nch == 2) o.f(" jit_vnb_update<%d>(vc%zu, vb%zu, vb%zu_m, lv%zu, llr_max, xo);\n", d, j, j, j, j);
-        else o.f(" jit_vn_update<%d, %d>(vc%zu, vb%zu, lv%zu, llr_max, xo);\n", d, it.nch, j, j, j);
-      }
-      if (ph != INNER) emit_out("xo", oc, strided, it.nch, ph == LAST);
-      o.f("      }\n");
-    };
-    auto emit_phases = [&](Phase ph) {
-      o.f("      {\n");
-      for (size_t j = 0; j < cn.size(); ++j) {
-        cn_load(j);
-        cn_update(j, ph);
-      }
-      o.f("      }\n      %sjit_barrier();\n", (var.abl & 4) ? "// " : "");
-      o.f("      {\n");
-      for (size_t j = 0; j < vn.size(); ++j) {
-        if (ph == LAST) {                                    // an item whose chunks are not part of the output has nothing left to do
-          unsigned oc[2];
-          bool strided;
-          out_offs(vn[j].idx, vn[j], oc, &strided);
-          if (!has_out(oc, vn[j].nch)) continue;
-        }
-        vn_load(j);
-        vn_update(j, ph);
-      }
-      o.f("      }\n");
-    };
-    if (lean_last) {
-      // The last trip is peeled out of the loop (num_iter is a launch parameter) and emitted from the LAST forms of the items: after
-      // the last check-node phase nobody reads a v2c again.  The state variant keeps the whole trip - its image is those v2c.
-      o.f("#pragma unroll 1\n    for (int it = 1; it < num_iter; ++it) {\n");
-      emit_phases(INNER);
-      o.f("      %sjit_barrier();\n    }\n", (var.abl & 4) ? "// " : "");
-      o.f("    if (num_iter > 0) {\n");
-      emit_phases(LAST);
-      // the next codeword's first stores go to slots only this wave touches after the CN phase: no barrier behind the
-      // last VN phase
-      o.f("    }\n");
-    } else {
-      o.f("#pragma unroll 1\n    for (int it = 0; it < num_iter; ++it) {\n      const bool last = it == num_iter - 1;\n      (void)last;\n");
-      emit_phases(BOTH);
-      // the next codeword's first stores go to slots only this wave touches after the CN phase: no barrier behind the
-      // last VN phase
-      o.f("      %sif (!last) jit_barrier();\n    }\n", (var.abl & 4) ? "// " : "");
-    }
-    if (var.state)
-      o.f("    if (st_out) { JIT_KEEP_BRANCH(); jit_barrier(); jit_copy_l2g(st_out + (size_t)b * %uu, %uu, %uu, %d, %d); jit_barrier(); }\n",
-          img_bytes / 4, msg0, img_bytes, w, nw);
-    o.f("  }\n}\n");
-  }
-  if (with_ops) {
-    const char* entry = phi ? (var.state ? "samd_ldpc5g_jit_phi_st" : "samd_ldpc5g_jit_phi") : (var.state ? "samd_ldpc5g_jit_st" : "samd_ldpc5g_jit");
-    o.f("\n// JIT_ENTRY %s\nextern \"C\" __global__ __launch_bounds__(%d) void %s(%s) {\n", entry, 64 * nw, entry, args);
-    o.f("  __shared__ float jit_smem[JIT_LDS_FLOATS];\n");
-    o.f("  if ((unsigned)(unsigned long)(jit_lds_f32*)jit_smem != 0u) __builtin_trap();\n");
-    o.f("  switch (jit_wave()) {\n");
-    for (int w = 0; w < nw; ++w)
-      o.f("    case %d: jit_wave_%d(llr_in, out, batch, num_iter, llr_max, offset, hard_out, ws, st_in, st_out); break;\n", w, w);
-    o.f("    default: break;\n  }\n}\n");
-  }
-  return o.s;
-}
-
-// ------------------------------------------------------------------------------------------------ hipRTC, bound lazily
-namespace {
-
-typedef struct samd_hiprtc_prog_* rtc_prog;   // opaque (hiprtcProgram)
-struct Rtc {
-  void* lib = nullptr;
-  int (*create)(rtc_prog*, const char*, const char*, int, const char* const*, const char* const*) = nullptr;
-  int (*compile)(rtc_prog, int, const char* const*) = nullptr;
-  int (*log_size)(rtc_prog, size_t*) = nullptr;
-  int (*log)(rtc_prog, char*) = nullptr;
-  int (*code_size)(rtc_prog, size_t*) = nullptr;
-  int (*code)(rtc_prog, char*) = nullptr;
-  int (*destroy)(rtc_prog*) = nullptr;
-  int (*version)(int*, int*) = nullptr;
-  bool ok = false;
-  std::string ver = "?";
-  Rtc() {
-    for (const char* name : {"libhiprtc.so", "libhiprtc.so.7", "/opt/rocm/lib/libhiprtc.so"}) {
-      lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (lib) break;
-    }
-    if (!lib) return;
-#define SAMD_RTC_SYM(field, sym) field = reinterpret_cast<decltype(field)>(dlsym(lib, sym))
-    SAMD_RTC_SYM(create, "hiprtcCreateProgram");
-    SAMD_RTC_SYM(compile, "hiprtcCompileProgram");
-    SAMD_RTC_SYM(log_size, "hiprtcGetProgramLogSize");
-    SAMD_RTC_SYM(log, "hiprtcGetProgramLog");
-    SAMD_RTC_SYM(code_size, "hiprtcGetCodeSize");
-    SAMD_RTC_SYM(code, "hiprtcGetCode");
-    SAMD_RTC_SYM(destroy, "hiprtcDestroyProgram");
-    SAMD_RTC_SYM(version, "hiprtcVersion");
-#undef SAMD_RTC_SYM
-    ok = create && compile && log_size && log && code_size && code && destroy;
-    int ma = 0, mi = 0;
-    if (version && version(&ma, &mi) == 0) ver = std::to_string(ma) + "." + std::to_string(mi);
-  }
-};
-Rtc& rtc() {
-  static Rtc r;
-  return r;
-}
-
-// ---- SHA-256 (FIPS 180-4) of the cache key: source text + compiler version + target
-struct Sha256 {
-  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-  unsigned char buf[64];
-  size_t fill = 0;
-  uint64_t total = 0;
-  static uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-  void block(const unsigned char* p) {
-    static const uint32_t K[64] = {
-        0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u,
-        0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu,
-        0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u,
-        0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-        0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u,
-        0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
-        0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-    uint32_t w[64];
-    for (int i = 0; i < 16; ++i) w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
-    for (int i = 16; i < 64; ++i) {
-      const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-      w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-    }
-    uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-    for (int i = 0; i < 64; ++i) {
-      const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K[i] + w[i];
-      const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-      hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-    }
-    h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-  }
-  void update(const void* data, size_t n) {
-    const unsigned char* p = (const unsigned char*)data;
-    total += n;
-    while (n) {
-      const size_t take = std::min(n, sizeof(buf) - fill);
-      memcpy(buf + fill, p, take);
-      fill += take; p += take; n -= take;
-      if (fill == 64) { block(buf); fill = 0; }
-    }
-  }
-  std::string hex() {
-    const uint64_t bits = total * 8;
-    const unsigned char one = 0x80, zero = 0;
-    update(&one, 1);
-    while (fill != 56) update(&zero, 1);
-    unsigned char len[8];
-    for (int i = 0; i < 8; ++i) len[i] = (unsigned char)(bits >> (56 - 8 * i));
-    update(len, 8);
-    char out[65];
-    for (int i = 0; i < 8; ++i) snprintf(out + 8 * i, 9, "%08x", h[i]);
-    return std::string(out, 64);
-  }
-};
-
-// Code objects on disk: compiling a kernel takes ~4 s (hipRTC) in EVERY process - eight ranks x every (code, rule, output form)
-// of a sweep.  <dir>/<sha256(source text | hipRTC version | target)>.co, dir = SAMD_JIT_CACHE_DIR, else
-// $XDG_CACHE_HOME/sionna_amd, else $HOME/.cache/sionna_amd (both read once, at library load: api.cpp); SAMD_JIT_CACHE=0: off.
-std::string cache_dir() {
-  if (opt_int("SAMD_JIT_CACHE", 1) == 0) return std::string();
-  std::string d = opt_str("SAMD_JIT_CACHE_DIR");
-  if (d.empty()) {
-    const std::string x = opt_str("SAMD__XDG_CACHE_HOME"), hm = opt_str("SAMD__HOME");
-    if (!x.empty()) d = x + "/sionna_amd";
-    else if (!hm.empty()) d = hm + "/.cache/sionna_amd";
-  }
-  return d;
-}
-void mkdirs(const std::string& path) {
-  for (size_t i = 1; i <= path.size(); ++i)
-    if (i == path.size() || path[i] == '/') (void)mkdir(path.substr(0, i).c_str(), 0755);
-}
-bool cache_read(const std::string& file, std::vector<char>* code) {
-  FILE* f = fopen(file.c_str(), "rb");
-  if (!f) return false;
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  bool ok = n > 64;
-  if (ok) {
-    code->resize((size_t)n);
-    ok = fread(code->data(), 1, (size_t)n, f) == (size_t)n && memcmp(code->data(), "\x7f" "ELF", 4) == 0;
-  }
-  fclose(f);
-  if (!ok) code->clear();
-  return ok;
-}
-void cache_write(const std::string& dir, const std::string& file, const std::vector<char>& code) {
-  mkdirs(dir);
-  const std::string tmp = file + ".tmp." + std::to_string((long)getpid());
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f) return;
-  const bool ok = fwrite(code.data(), 1, code.size(), f) == code.size();
-  fclose(f);
-  if (!ok || rename(tmp.c_str(), file.c_str()) != 0) (void)remove(tmp.c_str());   // rename: readers never see a partial file
-}
-
-// target of the code object: the architecture of the current device (the part of gcnArchName before the feature list);
-// without a device (SAMD_HOST_ONLY tools) the product's target
-std::string device_arch() {
-  int dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.gcnArchName[0]) {
-    std::string a = prop.gcnArchName;
-    const size_t c = a.find(':');
-    return c == std::string::npos ? a : a.substr(0, c);
-  }
-  (void)hipGetLastError();
-  return "gfx950";
-}
-
-// compiled code objects, shared by all handles of the same code (source text + target is the key)
-struct Compiled {
-  std::once_flag once;               // the compile (or the read of the cached code object) happens outside the map's lock
-  int status = 0;                    // 1 ok, -1 failed
-  bool from_disk = false;
-  std::string log, arch;
-  std::vector<char> code;
-  std::mutex mu;                     // fn
-  std::map<int, hipFunction_t> fn;   // per device; nullptr: the module did not load there
-  int waves = 16;                    // workgroup size / 64 of the generated kernel ("// JIT_WAVES n" in its source)
-  int group = 1, wgs = 0;            // any-lifting-size programs: codewords per workgroup, workgroups per CU (0: onchip_bp_grid)
-  std::string entry = "samd_ldpc5g_jit";   // the kernel's name ("// JIT_ENTRY name" in its source)
-  size_t img_bytes = 0;                      // state variant: bytes of the message image of one workgroup pass
-  size_t ws_bytes = 0;               // workspace row of one workgroup ("// JIT_WS_BYTES n"; 0: the messages fit LDS)
-};
-std::mutex g_mu;
-std::map<std::string, Compiled*> g_cache;
-std::atomic<long> g_compiles{0}, g_disk_hits{0};
-
-int compile_source(const std::string& src, Compiled* c) {
-  Rtc& r = rtc();
-  const std::string dir = cache_dir();
-  std::string file;
-  if (!dir.empty()) {
-    Sha256 sh;
-    sh.update(src.data(), src.size());
-    const std::string tail = "|hiprtc " + r.ver + "|" + c->arch;
-    sh.update(tail.data(), tail.size());
-    file = dir + "/" + sh.hex() + ".co";
-    if (cache_read(file, &c->code)) { c->from_disk = true; g_disk_hits.fetch_add(1); return 1; }
-  }
-  if (!r.ok) { c->log = "libhiprtc.so not available"; return -1; }
-  rtc_prog p = nullptr;
-  if (r.create(&p, src.c_str(), "samd_ldpc5g_jit.hip", 0, nullptr, nullptr) != 0) { c->log = "hiprtcCreateProgram failed"; return -1; }
-  // -ffp-contract=off: the node updates restate the reference's arithmetic literally (as the library's Makefile does)
-  const std::string arch_opt = "--offload-arch=" + c->arch;
-  const char* opts[] = {arch_opt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off"};
-  const int rc = r.compile(p, 4, opts);
-  g_compiles.fetch_add(1);
-  size_t ls = 0;
-  if (r.log_size(p, &ls) == 0 && ls > 1) {
-    c->log.resize(ls);
-    r.log(p, &c->log[0]);
-  }
-  if (rc != 0) { r.destroy(&p); return -1; }
-  size_t cs = 0;
-  if (r.code_size(p, &cs) != 0 || cs == 0) { r.destroy(&p); c->log += " (no code)"; return -1; }
-  c->code.resize(cs);
-  const int gc = r.code(p, c->code.data());
-  r.destroy(&p);
-  if (gc != 0) return -1;
-  if (!file.empty()) cache_write(dir, file, c->code);
-  return 1;
-}
-
-}  // namespace
+// the forms of a code's kernel: output form x rule x state
+constexpr int kVariants = 12;
+static int variant_slot(int rib, JitRule rule, int state) { return (rib ? 1 : 0) + 2 * (int)rule + (state ? 6 : 0); }
 
 struct JitState {
   std::mutex mu;
-  Compiled* variant[12] = {};   // by return_infobits + 2 * rule + 6 * state
-  int fn_dev[12] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};    // the device fn_cache[i] belongs to
-  hipFunction_t fn_cache[12] = {};
+  Compiled* variant[kVariants] = {};           // by variant_slot
+  int fn_dev[kVariants];                       // the device fn_cache[i] belongs to
+  hipFunction_t fn_cache[kVariants] = {};
   std::atomic<long> launches{0};               // decodes this handle ran on a specialised kernel
+  JitState() { std::fill(fn_dev, fn_dev + kVariants, -1); }
 };
-
-// rule of the generated kernel for a cn_mode: 0 offset-min-sum, 1 min-sum, 2 boxplus-phi (defined arithmetic); -1: none
-static int jit_rule(int cn_mode) {
-  return cn_mode == SAMD_CN_OFFSET_MINSUM ? 0 : cn_mode == SAMD_CN_MINSUM ? 1 : cn_mode == SAMD_CN_BOXPLUS_PHI ? 2 : -1;
-}
 
 static JitVariant jit_variant(int state) {
   JitVariant v;
@@ -1215,55 +28,26 @@ static JitVariant jit_variant(int state) {
   return v;
 }
 
-static Compiled* get_compiled(const samd_ldpc5g* h, int rib, int rule, int state = 0) {
+static Compiled* get_compiled(const samd_ldpc5g* h, int rib, JitRule rule, int state = 0) {
   JitState* st = h->jit_state;
-  const int vi = (rib ? 1 : 0) + 2 * rule + (state ? 6 : 0);
-  Compiled* c = nullptr;
+  const int vi = variant_slot(rib, rule, state);
   {
     std::lock_guard<std::mutex> lk(st->mu);
-    c = st->variant[vi];
+    if (st->variant[vi]) return st->variant[vi];
   }
-  std::string src;
-  if (!c) {
-    src = jit_generate_source(h, rib ? 1 : 0, rule, true, jit_variant(state ? 1 : 0));
-    if (src.empty()) {                                         // no such variant for this code (state: messages beyond LDS)
-      static Compiled* const none = [] {
-        Compiled* n = new Compiled();
-        n->status = -1;
-        n->log = "no generated kernel of this form for the code";
-        return n;
-      }();
-      return none;
-    }
-    const std::string arch = h->host_only ? std::string("gfx950") : device_arch();
-    std::lock_guard<std::mutex> gl(g_mu);
-    auto it = g_cache.find(arch + "|" + src);
-    if (it == g_cache.end()) {
-      c = new Compiled();
-      c->arch = arch;
-      const size_t wp = src.find("// JIT_WAVES ");
-      if (wp != std::string::npos) c->waves = atoi(src.c_str() + wp + 13);
-      const size_t gp = src.find("// JIT_GROUP "), sp = src.find("// JIT_WGS ");
-      if (gp != std::string::npos) c->group = std::max(1, atoi(src.c_str() + gp + 13));
-      if (sp != std::string::npos) c->wgs = std::max(1, atoi(src.c_str() + sp + 11));
-      const size_t wb = src.find("// JIT_WS_BYTES ");
-      if (wb != std::string::npos) c->ws_bytes = (size_t)atoll(src.c_str() + wb + 16);
-      const size_t ep = src.find("// JIT_ENTRY ");
-      if (ep != std::string::npos) c->entry = src.substr(ep + 13, src.find('\n', ep) - ep - 13);
-      const size_t ib = src.find("// JIT_IMG_BYTES ");
-      if (ib != std::string::npos) c->img_bytes = (size_t)atoll(src.c_str() + ib + 17);
-      g_cache.emplace(arch + "|" + src, c);
-    } else {
-      c = it->second;
-    }
+  JitProgram prog = jit_generate(h, rib ? 1 : 0, rule, true, jit_variant(state ? 1 : 0));
+  if (prog.source.empty()) {                                   // no such variant for this code (state: messages beyond LDS)
+    static Compiled* const none = [] {
+      Compiled* n = new Compiled();
+      n->status = -1;
+      n->log = "no generated kernel of this form for the code";
+      return n;
+    }();
+    return none;
   }
-  // compiling (or reading the cached code object) happens once per entry, outside g_mu: other codes and the launches of
-  // kernels that exist already do not wait for it
-  std::call_once(c->once, [&]() { c->status = compile_source(src, c); });
-  {
-    std::lock_guard<std::mutex> lk(st->mu);
-    st->variant[vi] = c;
-  }
+  Compiled* c = jit_compile(std::move(prog), h->host_only != 0);
+  std::lock_guard<std::mutex> lk(st->mu);
+  st->variant[vi] = c;
   return c;
 }
 
@@ -1281,7 +65,7 @@ static hipFunction_t get_function(const samd_ldpc5g* h, Compiled* c, int vi, int
     auto it = c->fn.find(dev);
     if (it == c->fn.end()) {
       hipModule_t mod = nullptr;
-      if (hipModuleLoadData(&mod, c->code.data()) != hipSuccess || hipModuleGetFunction(&fn, mod, c->entry.c_str()) != hipSuccess) {
+      if (hipModuleLoadData(&mod, c->code.data()) != hipSuccess || hipModuleGetFunction(&fn, mod, c->prog.entry.c_str()) != hipSuccess) {
         (void)hipGetLastError();
         fn = nullptr;
         c->log += " (the code object did not load on device " + std::to_string(dev) + ")";
@@ -1309,11 +93,12 @@ static int jit_grid(const samd_ldpc5g* h, int batch, int group, int wgs, int dev
 }
 
 size_t jit_workspace_bytes(const samd_ldpc5g* h, int batch, int cn_mode) {
-  const int rule = cn_mode == SAMD_CN_OFFSET_MINSUM ? 0 : cn_mode == SAMD_CN_MINSUM ? 1 : -1;
-  if (!h || !h->jit_plan || h->opt.jit <= 0 || rule < 0 || batch <= 0) return 0;
-  if (jit_class(h, false) != 2) return 0;
+  const JitRule rule = jit_rule(cn_mode);
+  const bool phi = rule == JitRule::BoxplusPhi;                // (whose programs never spill: 0)
+  if (!h || !h->jit_plan || h->opt.jit <= 0 || rule == JitRule::None || batch <= 0) return 0;
+  if (jit_class(h, phi) != 2) return 0;
   JitGeometry g;
-  if (!jit_geometry(h, false, &g) || g.ws_bytes == 0) return 0;
+  if (!jit_geometry(h, phi, &g) || g.ws_bytes == 0) return 0;
   int dev = 0;
   (void)hipGetDevice(&dev);
   return (size_t)jit_grid(h, batch, g.pairx ? 2 * g.G : g.G, g.wgs, dev) * g.ws_bytes + 256;
@@ -1322,18 +107,19 @@ size_t jit_workspace_bytes(const samd_ldpc5g* h, int batch, int cn_mode) {
 int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
                       float llr_max, float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes,
                       void* stream, const float* state_in, float* state_out) {
-  const int rule = jit_rule(cn_mode);
+  const JitRule rule = jit_rule(cn_mode);
+  const bool phi = rule == JitRule::BoxplusPhi;
   const int with_state = (state_in || state_out) ? 1 : 0;
-  if (!h->jit_state || h->opt.jit <= 0 || num_iter < 1 || rule < 0) return SAMD_ERR_UNSUPPORTED;
+  if (!h->jit_state || h->opt.jit <= 0 || num_iter < 1 || rule == JitRule::None) return SAMD_ERR_UNSUPPORTED;
   {
-    const int cls = jit_class(h, rule == 2);
+    const int cls = jit_class(h, phi);
     if (!cls) return SAMD_ERR_UNSUPPORTED;
-    if (rule == 2 && h->opt.jit_phi == 0) return SAMD_ERR_UNSUPPORTED;
-    if (rule == 2 && h->opt.jit_phi < 0 && cls == 2) {        // default: not where one codeword leaves lanes of its only chunk idle
+    if (phi && h->opt.jit_phi == 0) return SAMD_ERR_UNSUPPORTED;
+    if (phi && h->opt.jit_phi < 0 && cls == 2) {        // default: not where one codeword leaves lanes of its only chunk idle
       JitGeometry g;
       if (!jit_geometry(h, true, &g) || (g.G == 1 && g.P % 64 != 0)) return SAMD_ERR_UNSUPPORTED;
     }
-    if (rule == 2 && cls == 1 && (size_t)h->jit_plan->edges * h->z * 4 + 512 > 160 * 1024) return SAMD_ERR_UNSUPPORTED;
+    if (phi && cls == 1 && (size_t)h->jit_plan->edges * h->z * 4 + 512 > 160 * 1024) return SAMD_ERR_UNSUPPORTED;
   }
   if (h->opt.jit == 1 && batch < h->opt.jit_min_batch && !with_state) return SAMD_ERR_UNSUPPORTED;
   const int rib = return_infobits ? 1 : 0;
@@ -1344,16 +130,16 @@ int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int ba
   }
   int dev = 0;
   SAMD_HIP_CHECK(hipGetDevice(&dev));
-  hipFunction_t fn = get_function(h, c, rib + 2 * rule + 6 * with_state, dev);
+  hipFunction_t fn = get_function(h, c, variant_slot(rib, rule, with_state), dev);
   if (!fn) {
     set_error("specialised LDPC kernel unavailable: " + c->log);
     return SAMD_ERR_UNSUPPORTED;
   }
   float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
-  const int grid = jit_grid(h, batch, c->group, c->wgs, dev);
+  const int grid = jit_grid(h, batch, c->prog.group, c->prog.wgs, dev);
   float* ws = nullptr;
-  if (c->ws_bytes) {                                           // the last base rows' messages: a row per workgroup, caller-owned
-    const size_t need = (size_t)grid * c->ws_bytes + 256;
+  if (c->prog.ws_bytes) {                                           // the last base rows' messages: a row per workgroup, caller-owned
+    const size_t need = (size_t)grid * c->prog.ws_bytes + 256;
     if (!workspace || workspace_bytes < need) {
       set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
       return SAMD_ERR_WORKSPACE;
@@ -1362,7 +148,7 @@ int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int ba
   }
   void* args[] = {(void*)&llr, (void*)&out, (void*)&batch, (void*)&num_iter, (void*)&llr_max, (void*)&off, (void*)&hard_out, (void*)&ws,
                   (void*)&state_in, (void*)&state_out};
-  if (hipModuleLaunchKernel(fn, grid, 1, 1, 64 * (unsigned)c->waves, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess) {
+  if (hipModuleLaunchKernel(fn, grid, 1, 1, 64 * (unsigned)c->prog.waves, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess) {
     (void)hipGetLastError();
     set_error("specialised LDPC kernel: launch failed");
     return SAMD_ERR_UNSUPPORTED;                               // the caller's generic kernel takes the batch
@@ -1378,80 +164,6 @@ void free_jit(samd_ldpc5g* h) {
   h->jit_plan = nullptr;
   delete h->jit_state;          // compiled code stays in the process-wide cache
   h->jit_state = nullptr;
-}
-
-}  // namespace samd
-
-// ------------------------------------------------------------------------------------------------ decoder state (round 6)
-// return_state / msg_v2c (decoding.py:573, 636-637) on the generated kernels.  The state variant of a kernel moves the LDS image
-// of the message blocks of ONE workgroup pass (a codeword, or the group of codewords a workgroup decodes side by side) to and
-// from a caller's buffer, [passes][image floats], with contiguous 8-byte accesses.  What each float of the image is - which
-// codeword of the pass, which check node, which variable node of the lifted graph - is a function of the generator's layout:
-// state_map restates it for the host, which turns it into the reference's [num_edges, batch] order (edges sorted by variable
-// node, then check node) with samd_ldpc5g_state_convert_f32.
-namespace samd {
-static bool state_geometry(const samd_ldpc5g* h, int cn_mode, int* cls, JitGeometry* g, bool* lb, int* img_floats, int* cwpp) {
-  const int rule = jit_rule(cn_mode);
-  if (!h || !h->jit_plan || rule < 0) return false;
-  const bool phi = rule == 2;
-  *cls = jit_class(h, phi);
-  if (!*cls) return false;
-  const JitPlan& P = *h->jit_plan;
-  if (*cls == 1) {
-    *lb = h->z == 128;
-    *img_floats = P.edges * h->z;
-    *cwpp = 1;
-    return true;
-  }
-  if (!jit_geometry(h, phi, g) || g->spill_row >= 0) return false;
-  *lb = true;
-  *img_floats = g->e_lds * g->blk / 4;
-  *cwpp = g->pairx ? 2 * g->G : g->G;
-  return true;
-}
-
-static int state_map(const samd_ldpc5g* h, int cn_mode, int32_t* cw, int32_t* cn, int32_t* vn) {
-  int cls = 0, img = 0, cwpp = 1;
-  bool lb = false;
-  JitGeometry g;
-  if (!state_geometry(h, cn_mode, &cls, &g, &lb, &img, &cwpp)) return SAMD_ERR_UNSUPPORTED;
-  const JitPlan& P = *h->jit_plan;
-  const int z = h->z;
-  for (int q = 0; q < img; ++q) cw[q] = cn[q] = vn[q] = -1;
-  // edge block -> (base row, base column, shift)
-  std::vector<int> brow(P.edges, -1), bcol(P.edges, -1), bsh(P.edges, 0);
-  for (int r = 0; r < P.ncu; ++r)
-    for (int i = 0; i < P.row_deg[r]; ++i) brow[P.row_off[r] / (4 * z) + i] = r;
-  for (int c = 0; c < P.nbu; ++c)
-    for (auto& ed : P.col_edges[c]) {
-      const int e = ed.first / (4 * z);
-      if (e < 0 || e >= P.edges) return SAMD_ERR_INVALID;
-      bcol[e] = c;
-      bsh[e] = (ed.second / 4) % z;
-    }
-  for (int e = 0; e < P.edges; ++e) {
-    if (brow[e] < 0 || bcol[e] < 0) return SAMD_ERR_INVALID;
-    const int r = brow[e], c = bcol[e], s = bsh[e];
-    auto put = [&](int q, int j, int zc) {
-      if (r == P.prune_row && zc >= P.prune_z0) return;              // a pruned check node: its slot carries no edge
-      cw[q] = j; cn[q] = r * z + zc; vn[q] = c * z + (zc + s) % z;
-    };
-    if (cls == 1) {
-      for (int zc = 0; zc < z; ++zc) {
-        // interleaved (Z = 128): copy zc at float 2 (zc mod 64) + zc div 64 of its 128-float block; planar: float zc
-        const int f = lb ? 2 * (zc & 63) + (zc >> 6) : zc;
-        put(e * z + f, 0, zc);
-      }
-    } else {
-      const int bf = g.blk / 4;                                       // floats per edge block = 2 P
-      for (int p = 0; p < g.P; ++p) {
-        const int gq = p / g.H, zz = p % g.H;
-        if (g.pairx) { put(e * bf + 2 * p, 2 * gq, zz); put(e * bf + 2 * p + 1, 2 * gq + 1, zz); }
-        else { put(e * bf + 2 * p, gq, zz); put(e * bf + 2 * p + 1, gq, zz + g.H); }
-      }
-    }
-  }
-  return SAMD_OK;
 }
 
 // image [passes][img] <-> canonical [num_edges][batch] (logit sign: the state the reference returns is -1 x the internal v2c,
@@ -1525,20 +237,16 @@ __global__ __launch_bounds__(256) void state_convert_kernel(const int32_t* __res
 using namespace samd;
 
 extern "C" int samd_ldpc5g_state_layout(const samd_ldpc5g_t* h, int cn_mode, int* img_floats, int* cw_per_pass) {
-  int cls = 0, img = 0, cwpp = 1;
-  bool lb = false;
-  JitGeometry g;
-  if (!state_geometry(h, cn_mode, &cls, &g, &lb, &img, &cwpp)) { set_error("no generated kernel with state for this code / rule"); return SAMD_ERR_UNSUPPORTED; }
-  // (the variant must exist: a partly filled only chunk has no whole wave to move the image)
-  if (jit_generate_source(h, 1, jit_rule(cn_mode), false, jit_variant(1)).empty()) { set_error("no generated kernel with state for this code / rule"); return SAMD_ERR_UNSUPPORTED; }
-  if (img_floats) *img_floats = img;
-  if (cw_per_pass) *cw_per_pass = cwpp;
+  JitProgram p;   // (of the state variant, which must exist: a partly filled only chunk has no whole wave to move the image)
+  if (!jit_state_layout(h, jit_rule(cn_mode), &p)) { set_error("no generated kernel with state for this code / rule"); return SAMD_ERR_UNSUPPORTED; }
+  if (img_floats) *img_floats = (int)(p.img_bytes / 4);
+  if (cw_per_pass) *cw_per_pass = p.group;
   return SAMD_OK;
 }
 
 extern "C" int samd_ldpc5g_state_map(const samd_ldpc5g_t* h, int cn_mode, int32_t* cw, int32_t* cn, int32_t* vn) {
   SAMD_REQUIRE(h && cw && cn && vn, "null argument");
-  const int rc = state_map(h, cn_mode, cw, cn, vn);
+  const int rc = jit_state_map(h, jit_rule(cn_mode), cw, cn, vn);
   if (rc != SAMD_OK) set_error("no generated kernel with state for this code / rule");
   return rc;
 }
@@ -1572,9 +280,9 @@ extern "C" int samd_ldpc5g_jit_supported(const samd_ldpc5g_t* h) { return jit_el
 extern "C" long samd_ldpc5g_jit_source(const samd_ldpc5g_t* h, int return_infobits, int cn_mode, int with_ops, char* buf,
                                        size_t cap) {
   if (!jit_eligible(h)) { set_error("code outside the class of the specialised kernel"); return SAMD_ERR_UNSUPPORTED; }
-  if (jit_rule(cn_mode) < 0) { set_error("no specialised kernel for this rule"); return SAMD_ERR_UNSUPPORTED; }
+  if (jit_rule(cn_mode) == JitRule::None) { set_error("no specialised kernel for this rule"); return SAMD_ERR_UNSUPPORTED; }
   // (SAMD_JIT_STATE = 1: the text of the state variant, for tools and tests/jit_emu)
-  const std::string src = jit_generate_source(h, return_infobits ? 1 : 0, jit_rule(cn_mode), with_ops != 0, jit_variant((int)opt_int("SAMD_JIT_STATE", 0)));
+  const std::string src = jit_generate(h, return_infobits ? 1 : 0, jit_rule(cn_mode), with_ops != 0, jit_variant((int)opt_int("SAMD_JIT_STATE", 0))).source;
   if (src.empty()) { set_error("no generated kernel of this form for the code"); return SAMD_ERR_UNSUPPORTED; }
   if (buf && cap > 0) {
     const size_t n = std::min(cap - 1, src.size());
@@ -1588,7 +296,7 @@ extern "C" long samd_ldpc5g_jit_source(const samd_ldpc5g_t* h, int return_infobi
 // switched off, < 0 = compilation failed (samd_last_error holds the compiler's log)
 extern "C" int samd_ldpc5g_jit_prepare(const samd_ldpc5g_t* h, int return_infobits, int cn_mode) {
   if (!h || !h->jit_state || !jit_eligible(h) || h->opt.jit <= 0) return 0;
-  if (jit_rule(cn_mode) < 0) return 0;
+  if (jit_rule(cn_mode) == JitRule::None) return 0;
   Compiled* c = get_compiled(h, return_infobits ? 1 : 0, jit_rule(cn_mode));
   if (c->status != 1) { set_error("specialised LDPC kernel: " + c->log); return SAMD_ERR_HIP; }
   return 1;
@@ -1603,8 +311,7 @@ extern "C" long samd_ldpc5g_jit_launches(const samd_ldpc5g_t* h) {
 // process-wide counters of the code-object cache: what[0] = hipRTC compilations, what[1] = code objects read from disk
 extern "C" int samd_ldpc5g_jit_cache_stats(long* what) {
   if (!what) return SAMD_ERR_INVALID;
-  what[0] = g_compiles.load();
-  what[1] = g_disk_hits.load();
+  jit_compile_stats(what);
   return SAMD_OK;
 }
 

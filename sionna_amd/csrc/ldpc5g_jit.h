@@ -1,6 +1,7 @@
 // Specialised 5G LDPC decoders: the per-wave work lists of the explicit-message engine (ldpc5g_onchip_bp.hip builds
 // them, ldpc5g_decode_msg_kernel walks them with scalar code) turned into straight-line source for ONE code and
-// compiled at run time with hipRTC for gfx950 (ldpc5g_jit.cpp).
+// compiled at run time with hipRTC for gfx950 (ldpc5g_jit_gen.cpp writes the text, ldpc5g_jit_rtc.cpp compiles it,
+// ldpc5g_jit.cpp launches it).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -51,29 +52,53 @@ struct JitGeometry {
 struct JitState;
 
 // which form of a code's kernel is generated.  Everything else about the programs - schedule, message layout, lane geometry,
-// the form of each node update - follows from the code and the rule alone (ldpc5g_jit.cpp).
+// the form of each node update - follows from the code and the rule alone (ldpc5g_jit_gen.cpp).
 struct JitVariant {
   int state = 0;   // takes / returns the message image of a workgroup pass (return_state / msg_v2c)
   int abl = 0;     // -DSAMD_DEV builds: SAMD_JIT_ABL, parts of an iteration removed (see jit/ldpc5g_jit_templates.h)
 };
 
-// true when the code is in the class the generator covers (see jit_eligible in ldpc5g_jit.cpp)
+// rule of a generated kernel (the values are part of the variant index); boxplus-phi on the defined exp / log
+enum class JitRule { None = -1, OffsetMinSum = 0, MinSum = 1, BoxplusPhi = 2 };
+JitRule jit_rule(int cn_mode);   // the one mapping from SAMD_CN_*; None: no generated kernel for the rule
+
+// What the generator hands the runtime: the translation unit for hipRTC and, as data, what a launch must know about it.  The
+// text carries the same numbers as `// JIT_*` comment lines for tests and tools; nothing reads them back.
+struct JitProgram {
+  std::string source;      // empty: no such variant for the code
+  std::string entry;       // the kernel's name
+  int waves = 0;           // workgroup size / 64
+  int group = 1;           // codewords a workgroup decodes in one pass
+  int wgs = 0;             // workgroups per CU (0: the grid of onchip_bp_grid)
+  size_t ws_bytes = 0;     // workspace row of one workgroup (0: the messages fit LDS)
+  unsigned img_bytes = 0;  // state variant: bytes of the message image of one workgroup pass ...
+  unsigned img_msg0 = 0;   // ... and where it starts in LDS
+  bool layout_b = false;   // the two chunks of an edge block interleaved (jit/ldpc5g_jit_templates.h: JIT_LAYOUT_B)
+};
+
+// ---- the generator (ldpc5g_jit_gen.cpp): host code, functions of the code and the rule alone
+// true when the code is in the class the generator covers
 bool jit_eligible(const samd_ldpc5g* h);
-// the whole translation unit handed to hipRTC.  with_ops = false: without the gfx950 operation definitions and the
-// __global__ entry (what tests/jit_emu compiles for the CPU)
-// rule: 0 offset-min-sum, 1 min-sum, 2 boxplus-phi on the defined exp / log
-std::string jit_generate_source(const samd_ldpc5g* h, int return_infobits, int rule, bool with_ops, JitVariant variant);
+// with_ops = false: without the gfx950 operation definitions and the __global__ entry (what tests/jit_emu compiles for the CPU)
+JitProgram jit_generate(const samd_ldpc5g* h, int return_infobits, JitRule rule, bool with_ops, JitVariant variant);
+// the state variant's image: img_bytes, group and layout_b as jit_generate fills them, without the text (g: the lane geometry
+// of class 2).  Returns the class; 0: no such variant
+int jit_state_layout(const samd_ldpc5g* h, JitRule rule, JitProgram* p, JitGeometry* g = nullptr);
+// per float of that image: codeword of the pass, check node, variable node (-1: the slot carries no edge); SAMD_OK or an error
+int jit_state_map(const samd_ldpc5g* h, JitRule rule, int32_t* cw, int32_t* cn, int32_t* vn);
+// graph data of the generator for a code that build_onchip_bp_tables left without a plan (any even lifting size)
+void build_jit_plan_general(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
+// 0: no generated kernel; 1: the Z = 128 k class (whole chunks of one kind, constants); 2: any-lifting-size programs
+int jit_class(const samd_ldpc5g* h, bool phi);
+bool jit_geometry(const samd_ldpc5g* h, bool phi, JitGeometry* g);
+
+// ---- the launch path (ldpc5g_jit.cpp)
 // SAMD_OK, SAMD_ERR_UNSUPPORTED (caller runs the generic kernel) or an error
 int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
                       float llr_max, float offset, int hard_out, int return_infobits, void* workspace, size_t workspace_bytes,
                       void* stream, const float* state_in = nullptr, float* state_out = nullptr);
 // workspace the generated kernel of this code needs for `batch` codewords (0: none - the messages fit LDS - or no such kernel)
 size_t jit_workspace_bytes(const samd_ldpc5g* h, int batch, int cn_mode);
-// graph data of the generator for a code that build_onchip_bp_tables left without a plan (any even lifting size)
-void build_jit_plan_general(samd_ldpc5g* h, const std::vector<std::vector<std::pair<int, int>>>& by_row);
-// 0: no generated kernel; 1: the Z = 128 k class (whole chunks of one kind, constants); 2: any-lifting-size programs
-int jit_class(const samd_ldpc5g* h, bool phi);
-bool jit_geometry(const samd_ldpc5g* h, bool phi, JitGeometry* g);
 JitState* new_jit_state();
 void free_jit(samd_ldpc5g* h);
 

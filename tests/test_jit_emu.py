@@ -1,4 +1,4 @@
-"""The specialised 5G LDPC decoder (csrc/ldpc5g_jit.cpp) held to the oracle WITHOUT a GPU.
+"""The specialised 5G LDPC decoder (csrc/ldpc5g_jit_gen.cpp) held to the oracle WITHOUT a GPU.
 
 libsionna_amd.so generates, for one code, straight-line per-wave programs (block offsets, shifts, rate-matching offsets as
 constants) and compiles them with hipRTC for gfx950.  The generator is host code: here it runs on a handle built under

@@ -1,6 +1,6 @@
 """The generated min-sum programs with the LAST iteration peeled and lean, held to the oracle without a GPU.
 
-After the last check-node phase nobody reads a v2c again, so the generator (csrc/ldpc5g_jit.cpp) emits the last iteration of the
+After the last check-node phase nobody reads a v2c again, so the generator (csrc/ldpc5g_jit_gen.cpp) emits the last iteration of the
 min-sum / offset-min-sum programs of the Z = 128 k class from `last` forms of the item bodies: the variable-node items of the
 output columns form their totals (jit_vnb_total / jit_vn_total) and store nothing, the other columns have no item, and the
 check-node items form and store c2v only for the edges those items read (the KEEP mask of jit_cn_update).  The state variant,

@@ -1,4 +1,4 @@
-"""Source / code object / ISA statistics of the specialised 5G LDPC decoder (csrc/ldpc5g_jit.cpp) for one code.
+"""Source / code object / ISA statistics of the specialised 5G LDPC decoder (csrc/ldpc5g_jit_gen.cpp) for one code.
 
 Runs WITHOUT a GPU: the handle is built under SAMD_HOST_ONLY (tables and schedules only), the source generator and
 hipRTC are host code.  `python tools/jit_dump.py --k 2816 --n 8448 --m 6 --bg bg1 --out /tmp/jit` writes

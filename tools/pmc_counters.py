@@ -21,15 +21,15 @@ KERNELS = {   # key -> (substring of the kernel name, unit, source file(s): the 
     # the explicit-message engine, by its last template argument: the check-node rule (2 min-sum, 1 boxplus-phi)
     # (round 3: the grouped-dispatch kernel <ZM = 2 (Z = 128), LLRG, rule, VAR>; rule 2 min-sum, 1 boxplus-phi on the
     # defined exp / log, 4 boxplus-phi on the hardware transcendentals)
-    # the kernel GENERATED for the code (csrc/ldpc5g_jit.cpp, compiled by hipRTC at run time): generator, node updates,
+    # the kernel GENERATED for the code (csrc/ldpc5g_jit_gen.cpp, compiled by hipRTC at run time): generator, node updates,
     # operation definitions; the schedule it writes out comes from the table builder in ldpc5g_onchip_bp.hip
     # (a trailing $: the kernel's exact name - the generated kernels carry the rule and the code in theirs)
-    "ldpc5g_jit": ("samd_ldpc5g_jit$", "decode", ["sionna_amd/csrc/ldpc5g_jit.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
+    "ldpc5g_jit": ("samd_ldpc5g_jit$", "decode", ["sionna_amd/csrc/ldpc5g_jit_gen.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
                                                   "sionna_amd/csrc/jit/ldpc5g_jit_ops_gfx950.h", "sionna_amd/csrc/ldpc5g_onchip_bp.hip"]),
     # round 6: boxplus-phi on the generated kernel (rolled check-node loops) at C2, and the any-lifting-size programs at C4's code
-    "ldpc5g_jit_phi": ("samd_ldpc5g_jit_phi$", "decode", ["sionna_amd/csrc/ldpc5g_jit.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
+    "ldpc5g_jit_phi": ("samd_ldpc5g_jit_phi$", "decode", ["sionna_amd/csrc/ldpc5g_jit_gen.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
                                                           "sionna_amd/csrc/jit/ldpc5g_jit_ops_gfx950.h", "sionna_amd/csrc/ldpc5g_onchip_bp.hip"]),
-    "ldpc5g_jit_c4": ("samd_ldpc5g_jit_ms_bg2z80k768n1536$", "decode", ["sionna_amd/csrc/ldpc5g_jit.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
+    "ldpc5g_jit_c4": ("samd_ldpc5g_jit_ms_bg2z80k768n1536$", "decode", ["sionna_amd/csrc/ldpc5g_jit_gen.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
                                                                         "sionna_amd/csrc/jit/ldpc5g_jit_ops_gfx950.h"]),
     "ldpc5g_ms": ("ldpc5g_decode_msg_kernel<2, true, 2, 1>", "decode", "sionna_amd/csrc/ldpc5g_onchip_ms.inc"),
     "ldpc5g_bp": ("ldpc5g_decode_msg_kernel<2, true, 1, 0>", "decode", "sionna_amd/csrc/ldpc5g_onchip_ms.inc"),
