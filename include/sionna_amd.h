@@ -334,6 +334,40 @@ int samd_binary_source_f32(uint64_t seed, uint64_t call, int64_t n, float* out, 
 int samd_awgn_c64(const float* x, const float* no, int64_t no_len, uint64_t seed,
                   uint64_t call, int64_t n, float* y, void* stream);
 
+/* Discrete channels (csrc/discrete.hip), one streaming launch: channel/discrete_channel.py
+ *   kind 0  BinaryMemorylessChannel.call :238-296 (BinarySymmetricChannel :376-385: pb0 = pb1; BinaryZChannel :470-478:
+ *           pb0 = NULL, read as 0) with the error pattern of _sample_errors :191-222 drawn directly and _custom_xor :168-179
+ *   kind 1  BinaryErasureChannel.call :564-596 (pb1 alone is read, rounded to float32 as :570 does)
+ * x, y [n] of the entry's type (y may be x); element i of the flattened input reads pb0 / pb1 at index
+ * (i % pb_len) * pb_stride (DEVICE, float32; float64 for _f64): pb_len = 1 a scalar, stride 2 with pb1 = pb0 + 1 a [..., 2]
+ * tensor.  Element i uses word i % 4 of the Philox block i / 4 of (seed, call); the error event is
+ * word < ceil(p 2^32), p = pb clipped to [0, 1] with NaN -> 0 (DESIGN.md "Discrete channels").  bipolar: the input is
+ * -1 / 1 instead of 0 / 1.  return_llrs (_f32 / _f64 only): kind 0 log((1 - pb1 - eps) / (pb0 + eps)) for a received
+ * 1 and log((pb1 + eps) / (1 - pb0 - eps)) for a received 0, eps = 1e-9, each log correctly rounded in float32, clipped to
+ * +-llr_max; kind 1 +-llr_max or 0 where erased.  Hard outputs: the flipped value; kind 1 x or the erased element (-1,
+ * or 0 for bipolar input).  _u8 takes neither bipolar input nor kind 1.  tests/discrete_f32.py is the specification. */
+int samd_discrete_channel_f32(const float* x, const float* pb0, const float* pb1, int64_t pb_stride, int64_t pb_len,
+                              int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                              int64_t n, float* y, void* stream);
+int samd_discrete_channel_f64(const double* x, const double* pb0, const double* pb1, int64_t pb_stride, int64_t pb_len,
+                              int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                              int64_t n, double* y, void* stream);
+int samd_discrete_channel_i8(const int8_t* x, const float* pb0, const float* pb1, int64_t pb_stride, int64_t pb_len,
+                             int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                             int64_t n, int8_t* y, void* stream);
+int samd_discrete_channel_u8(const uint8_t* x, const float* pb0, const float* pb1, int64_t pb_stride, int64_t pb_len,
+                             int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                             int64_t n, uint8_t* y, void* stream);
+int samd_discrete_channel_i16(const int16_t* x, const float* pb0, const float* pb1, int64_t pb_stride, int64_t pb_len,
+                              int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                              int64_t n, int16_t* y, void* stream);
+int samd_discrete_channel_i32(const int32_t* x, const float* pb0, const float* pb1, int64_t pb_stride, int64_t pb_len,
+                              int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                              int64_t n, int32_t* y, void* stream);
+int samd_discrete_channel_i64(const int64_t* x, const float* pb0, const float* pb1, int64_t pb_stride, int64_t pb_len,
+                              int kind, int bipolar, int return_llrs, double llr_max, uint64_t seed, uint64_t call,
+                              int64_t n, int64_t* y, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * OFDM resource grid, frequency-domain channel, LS estimation, LMMSE equalisation
  * (config C4 of the north star).  S below = num_tx * num_streams_per_tx, RE index = t*F + f.

@@ -140,6 +140,8 @@ _SIGNATURES = {
     "samd_binary_source_f32": (_i32, [_u64, _u64, _i64, _vp, _vp]),
     "samd_awgn_c64": (_i32, [_vp, _vp, _i64, _u64, _u64, _i64, _vp, _vp]),
     "samd_rg_map_c64": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    **{f"samd_discrete_channel_{t}": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _f64, _u64, _u64, _i64, _vp, _vp])
+       for t in ("f32", "f64", "i8", "u8", "i16", "i32", "i64")},
     "samd_gather3": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_tdl_cir_c64": (_i32, [_u64, _u64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _f32, _f32, _i32, _f32,
                                 _f32, _vp, _vp]),

@@ -1,5 +1,6 @@
 """Channel models of the hot path (mirror of ``sionna.phy.channel``)."""
 from .awgn import AWGN
+from .discrete_channel import BinaryMemorylessChannel, BinarySymmetricChannel, BinaryZChannel, BinaryErasureChannel
 from .utils import subcarrier_frequencies, cir_to_ofdm_channel, time_to_ofdm_channel
 from .ofdm_channel import GenerateOFDMChannel, ApplyOFDMChannel, OFDMChannel, RayleighBlockFading
 from .time_channel import (time_lag_discrete_time_channel, cir_to_time_channel, GenerateTimeChannel,

@@ -191,7 +191,8 @@ def make_tf():
     tf.__doc__ = "NumPy stand-in (tools/ref_exec/tf_numpy.py)"
     tf.Tensor, tf.RaggedTensor = Tensor, RaggedTensor
     tf.TensorShape = type("TensorShape", (), {})           # shapes are tuples here: nothing is an instance of it
-    for name in ("float16", "float32", "float64", "int8", "int16", "int32", "int64", "uint8", "complex64", "complex128", "bool"):
+    for name in ("float16", "float32", "float64", "int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "complex64",
+                 "complex128", "bool"):
         setattr(tf, name, DType(name))
     tf.bfloat16 = type("BF16", (), {"__eq__": lambda self, o: False, "__hash__": lambda self: 0, "__repr__": lambda self: "tf.bfloat16"})()   # (no NumPy twin; only ever compared)
     tf.DType, tf.dtypes = DType, types.SimpleNamespace(DType=DType)
@@ -473,6 +474,8 @@ def make_tf():
     def function(func=None, **k):
         return (lambda f: f) if func is None else func
     tf.function = function
+    # tf.custom_gradient: f returns (value, grad_fn); without a tape only the value is of interest (channel/discrete_channel.py)
+    tf.custom_gradient = lambda f: (lambda *a, **k: f(*a, **k)[0])
 
     def py_function(func, inp, Tout, name=None):
         r = func(*[_t(np.asarray(a)) for a in inp])
