@@ -94,7 +94,8 @@ def per_iteration_stats(asm, waves=16):
     """The kernel is `waves` wave programs.  With the last iteration inside the loop (boxplus-phi, the state variant) a program is
     [prologue + init | barrier | CN phase | barrier | VN phase | barrier]; with the last iteration peeled (min-sum) it is
     [prologue + init | barrier | CN phase | barrier | VN phase | barrier | last CN phase | barrier | last VN phase] and the last
-    VN phase, which no barrier follows, is counted with the next program's prologue under per_codeword.  Instruction classes and
+    VN phase, which no barrier follows, is counted with the next program's prologue under per_codeword; with the first iteration
+    lean as well, [first CN phase | barrier | first VN phase | barrier] stand in front of the loop.  Instruction classes and
     LDS-pipeline cycles of ONE iteration summed over the waves (what a CU executes per iteration and codeword)."""
     body = asm[re.search(r"<samd_ldpc5g_jit\w*>:", asm).start():]
     segs = [[]]
@@ -105,10 +106,16 @@ def per_iteration_stats(asm, waves=16):
         segs[-1].append(mm.group(1))
         if mm.group(1) == "s_barrier":
             segs.append([])
-    per = (len(segs) - 1) // waves                            # barriers of one wave program: 3, or 4 with a peeled last iteration
-    parts = [("cn_phase", segs[1::per]), ("vn_phase", segs[2::per]), ("per_codeword", segs[0:-1:per] + (segs[-1:] if per == 4 else []))]
-    if per == 4:
-        parts.insert(2, ("last_cn_phase", segs[3::per]))
+    per = (len(segs) - 1) // waves                            # barriers of one wave program: 3, 4 with a peeled last iteration, 6
+    if per == 6:
+        # ... and with a lean first iteration: [prologue + init | barrier | first CN phase | barrier | first VN phase | barrier |
+        # CN phase | ... as above]
+        parts = [("cn_phase", segs[3::per]), ("vn_phase", segs[4::per]), ("first_cn_phase", segs[1::per]), ("first_vn_phase", segs[2::per]),
+                 ("last_cn_phase", segs[5::per]), ("per_codeword", segs[0:-1:per] + segs[-1:])]
+    else:
+        parts = [("cn_phase", segs[1::per]), ("vn_phase", segs[2::per]), ("per_codeword", segs[0:-1:per] + (segs[-1:] if per == 4 else []))]
+        if per == 4:
+            parts.insert(2, ("last_cn_phase", segs[3::per]))
     out = {}
     for name, sel in parts:
         ops = [o for sg in sel for o in sg]

@@ -25,6 +25,7 @@ KERNELS = {   # key -> (substring of the kernel name, unit, source file(s): the 
     # operation definitions; the schedule it writes out comes from the table builder in ldpc5g_onchip_bp.hip
     # (a trailing $: the kernel's exact name - the generated kernels carry the rule and the code in theirs)
     "ldpc5g_jit": ("samd_ldpc5g_jit$", "decode", ["sionna_amd/csrc/ldpc5g_jit_gen.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
+                                                  "sionna_amd/csrc/jit/ldpc5g_jit_first.h",
                                                   "sionna_amd/csrc/jit/ldpc5g_jit_ops_gfx950.h", "sionna_amd/csrc/ldpc5g_onchip_bp.hip"]),
     # round 6: boxplus-phi on the generated kernel (rolled check-node loops) at C2, and the any-lifting-size programs at C4's code
     "ldpc5g_jit_phi": ("samd_ldpc5g_jit_phi$", "decode", ["sionna_amd/csrc/ldpc5g_jit_gen.cpp", "sionna_amd/csrc/jit/ldpc5g_jit_templates.h",
@@ -73,14 +74,23 @@ def jit_static(k=2816, n=8448, m=6, bg="bg1", num_iter=20):
     per_it = {kk: it["cn_phase"][kk] + it["vn_phase"][kk] for kk in keys}
     out = {"per_iteration": per_it, "per_codeword": {kk: it["per_codeword"][kk] for kk in keys},
            "lds_mix_cn": it["cn_phase"]["lds_mix"], "lds_mix_vn": it["vn_phase"]["lds_mix"], "num_iter": num_iter}
+    # a lean first iteration: its two phases, and one trip fewer of the loop
+    first = {kk: it["first_cn_phase"][kk] + it["first_vn_phase"][kk] for kk in keys} if "first_cn_phase" in it else None
+    if first:
+        out["first_iteration"] = first
+        out["lds_mix_first_cn"], out["lds_mix_first_vn"] = it["first_cn_phase"]["lds_mix"], it["first_vn_phase"]["lds_mix"]
+    trips = num_iter - 2 if first else num_iter - 1          # of the loop, in front of the peeled last trip
     if "last_cn_phase" in it:
         # the last iteration is peeled and lean: num_iter - 1 trips of the loop, the last check-node phase, and the last
         # variable-node phase, which per_iteration_stats counts under per_codeword
         out["last_cn_phase"] = {kk: it["last_cn_phase"][kk] for kk in keys}
         out["lds_mix_last_cn"] = it["last_cn_phase"]["lds_mix"]
-        out["lds_pipe_cycles_per_unit"] = ((num_iter - 1) * per_it["lds_pipe_cycles"] + it["last_cn_phase"]["lds_pipe_cycles"]
-                                           + it["per_codeword"]["lds_pipe_cycles"])
-        out["valu_insts_per_unit"] = (num_iter - 1) * per_it["valu"] + it["last_cn_phase"]["valu"] + it["per_codeword"]["valu"]
+        out["lds_pipe_cycles_per_unit"] = (trips * per_it["lds_pipe_cycles"] + it["last_cn_phase"]["lds_pipe_cycles"]
+                                           + it["per_codeword"]["lds_pipe_cycles"] + (first["lds_pipe_cycles"] if first else 0))
+        out["valu_insts_per_unit"] = (trips * per_it["valu"] + it["last_cn_phase"]["valu"] + it["per_codeword"]["valu"]
+                                      + (first["valu"] if first else 0))
+        out["lds_insts_per_unit"] = (trips * per_it["lds_insts"] + it["last_cn_phase"]["lds_insts"] + it["per_codeword"]["lds_insts"]
+                                     + (first["lds_insts"] if first else 0))
     else:
         out["lds_pipe_cycles_per_unit"] = num_iter * per_it["lds_pipe_cycles"] + it["per_codeword"]["lds_pipe_cycles"]
         out["valu_insts_per_unit"] = num_iter * per_it["valu"] + it["per_codeword"]["valu"]
