@@ -135,28 +135,34 @@ class CDL(Object):
     def delay_spread(self, value):
         self._delay_spread = float(value)
 
+    def _host_tables(self):
+        """The kernel's tables as NumPy arrays in the block's precision (what ``_tables`` sends to the device), in the order of
+        ``_tables``: f_rx, f_tx, a_rx, a_tx, r_rx, pol_rx, pol_tx, order, amp, los (or None), xpr_scale, two_pi_over_lambda."""
+        lam = SPEED_OF_LIGHT / self._carrier_frequency
+        f_rx, a_rx, r_rx = _side_tables(self._rx_array, self._rx_o, self._rays["zoa"], self._rays["aoa"], lam)
+        f_tx, a_tx, _ = _side_tables(self._tx_array, self._tx_o, self._rays["zod"], self._rays["aod"], lam)
+        amp = np.sqrt(self._powers / self.NUM_RAYS)
+        los = None
+        if self._los:
+            one = lambda v: np.array([[v]])
+            lf_rx, la_rx, lr_rx = _side_tables(self._rx_array, self._rx_o, one(self._los_ang["zoa"]), one(self._los_ang["aoa"]), lam)
+            lf_tx, la_tx, _ = _side_tables(self._tx_array, self._tx_o, one(self._los_ang["zod"]), one(self._los_ang["aod"]), lam)
+            kf = self._k_factor
+            amp = amp * np.sqrt(1 / (kf + 1))
+            c2f = lambda z: np.stack([z.real, z.imag], -1).reshape(-1)
+            los = np.concatenate([lf_rx.reshape(-1), lf_tx.reshape(-1), c2f(la_rx.reshape(-1)), c2f(la_tx.reshape(-1)),
+                                  lr_rx.reshape(-1), [np.sqrt(kf / (kf + 1))]])
+        f32 = lambda x: np.ascontiguousarray(x, self._np_rdtype)
+        c64 = lambda x: np.ascontiguousarray(x, self._np_cdtype)
+        i32 = lambda x: np.ascontiguousarray(x, np.int32)
+        return (f32(f_rx), f32(f_tx), c64(a_rx), c64(a_tx), f32(r_rx), i32(self._rx_array.pol_index()),
+                i32(self._tx_array.pol_index()), i32(self._order), f32(amp), f32(los) if los is not None else None,
+                float(np.sqrt(1 / self._xpr)), float(2 * PI / lam))
+
     def _tables(self):
         if self._dev is None:
-            lam = SPEED_OF_LIGHT / self._carrier_frequency
-            f_rx, a_rx, r_rx = _side_tables(self._rx_array, self._rx_o, self._rays["zoa"], self._rays["aoa"], lam)
-            f_tx, a_tx, _ = _side_tables(self._tx_array, self._tx_o, self._rays["zod"], self._rays["aod"], lam)
-            amp = np.sqrt(self._powers / self.NUM_RAYS)
-            los = None
-            if self._los:
-                one = lambda v: np.array([[v]])
-                lf_rx, la_rx, lr_rx = _side_tables(self._rx_array, self._rx_o, one(self._los_ang["zoa"]), one(self._los_ang["aoa"]), lam)
-                lf_tx, la_tx, _ = _side_tables(self._tx_array, self._tx_o, one(self._los_ang["zod"]), one(self._los_ang["aod"]), lam)
-                kf = self._k_factor
-                amp = amp * np.sqrt(1 / (kf + 1))
-                c2f = lambda z: np.stack([z.real, z.imag], -1).reshape(-1)
-                los = np.concatenate([lf_rx.reshape(-1), lf_tx.reshape(-1), c2f(la_rx.reshape(-1)), c2f(la_tx.reshape(-1)),
-                                      lr_rx.reshape(-1), [np.sqrt(kf / (kf + 1))]])
-            f32 = lambda x: _ffi.to_device(np.ascontiguousarray(x, self._np_rdtype), self.rdtype)
-            c64 = lambda x: _ffi.to_device(np.ascontiguousarray(x, self._np_cdtype), self.cdtype)
-            i32 = lambda x: _ffi.to_device(np.ascontiguousarray(x, np.int32), torch.int32)
-            self._dev = (f32(f_rx), f32(f_tx), c64(a_rx), c64(a_tx), f32(r_rx), i32(self._rx_array.pol_index()),
-                         i32(self._tx_array.pol_index()), i32(self._order), f32(amp), f32(los) if los is not None else None,
-                         float(np.sqrt(1 / self._xpr)), float(2 * PI / lam))
+            td = {np.dtype(np.int32): torch.int32, np.dtype(self._np_rdtype): self.rdtype, np.dtype(self._np_cdtype): self.cdtype}
+            self._dev = tuple(_ffi.to_device(x, td[x.dtype]) if isinstance(x, np.ndarray) else x for x in self._host_tables())
         return self._dev
 
     def __call__(self, batch_size, num_time_steps, sampling_frequency):
@@ -168,6 +174,8 @@ class CDL(Object):
         for _ in range(7):                                      # the kernel consumes calls call .. call+7
             rng.next_call()
         a = torch.empty((b, 1, u, 1, s, n, t), dtype=self.cdtype, device=_ffi.device())
+        if b == 0:                                              # nothing to launch (the entry requires batch > 0); the stream has advanced
+            return wrap(a), wrap(torch.empty((0, 1, 1, n), dtype=self.rdtype, device=a.device))
         ws, ws_bytes = self._ws.get(_ffi.lib().samd_cdl_workspace_bytes(b, n))
         _ffi.check((_ffi.lib().samd_cdl_cir_c128 if self.precision == "double" else _ffi.lib().samd_cdl_cir_c64)(rng.seed, call, b, n, u, s, t, float(sampling_frequency), _ffi.ptr(f_rx),
                                                _ffi.ptr(f_tx), _ffi.ptr(a_rx), _ffi.ptr(a_tx), _ffi.ptr(r_rx), _ffi.ptr(pol_rx),

@@ -576,3 +576,170 @@ def apt_model_f32(x, h, link_scale=None, mutation=None):
     y = np.empty((b_n, rx_n, ra_n, tout), np.complex64)
     y.real, y.imag = yx, yy
     return y
+
+
+# ------------------------------------------------------------------ TDL / CDL tap generators (csrc/ofdm.hip, csrc/cdl.hip)
+def _uni32(seed, call, n, lo, hi):
+    """``uni`` / ``unir<float>``: lo + (hi - lo) * u01(word i % 4 of Philox block i / 4), every operation in float32"""
+    from oracle import utils as outil
+    w = np.stack(outil.philox_block(seed, call, (n + 3) // 4), axis=1).reshape(-1)[:n]
+    lo, hi = F(lo), F(hi)
+    return (lo + (hi - lo) * outil._u01(w)).astype(F)
+
+
+PI_F = F(3.14159265358979323846)
+
+
+def tdl_cir_model(seed, call, batch, num_time_steps, sampling_frequency, mean_powers, min_doppler, max_doppler, num_rx_ant=1,
+                  num_tx_ant=1, num_sinusoids=20, los_power=None, los_aoa=np.pi / 4, fault=None):
+    """Model of tdl_cir_kernel in float32, operation for operation: chunks of 16 time steps, the first step of a chunk evaluated
+    directly, the others by the packed rotation v <- v cw + (-v.y, v.x) sw; the draws once per thread (N <= 24) or once per chunk.
+    ``fault``: a seeded one-line fault (tests/test_tap_channel_host.py).  -> complex64 [B, 1, RA, 1, TA, P, T]"""
+    b_, ra, ta, t_, n_ = int(batch), int(num_rx_ant), int(num_tx_ant), int(num_time_steps), int(num_sinusoids)
+    mp = np.asarray(mean_powers, F)
+    p_ = len(mp)
+    fs = F(sampling_frequency)
+    pi = F(np.nextafter(PI_F, F(4))) if fault == "pi_ulp" else PI_F
+    kchunk, kmaxsin = 16, 24
+    doppler = _uni32(seed, call, b_, min_doppler, max_doppler).reshape(b_, 1, 1, 1)
+    fn = F(n_)
+    theta_all = _uni32(seed, call + 1, b_ * p_ * n_, -pi / fn, pi / fn).reshape(b_, 1, 1, p_, n_)
+    phi_all = _uni32(seed, call + 2, b_ * ra * ta * p_ * n_, -pi, pi).reshape(b_, ra, ta, p_, n_)
+    phi0 = _uni32(seed, call + 3, b_, -pi, pi).reshape(b_, 1, 1)
+    amp = np.sqrt(mp).reshape(1, 1, 1, p_)
+    norm = F(1) / np.sqrt(fn)
+    cached = n_ <= kmaxsin
+
+    def draw(n):
+        theta = theta_all[..., n]
+        if fault == "theta_no_p" and not cached:                                   # (b * N + n) instead of ((b * P + p) * N + n)
+            flat = theta_all.reshape(-1)
+            theta = flat[(np.arange(b_) * n_ + n)].reshape(b_, 1, 1, 1) * np.ones((1, 1, 1, p_), F)
+        return np.cos((F(2) * PI_F / fn) * F(n + 1) + theta).astype(F), phi_all[..., n]
+
+    out = np.zeros((b_, ra, ta, p_, t_), np.complex64)
+    los = los_power is not None
+    p_los = 1 if fault == "los_p1" else 0
+    chain = {}                                                                     # fault "no_reanchor": v carried across chunks
+    for t0 in range(0, t_, kchunk):
+        kmax = min(t_ - t0, kchunk)
+        accx = np.zeros((kchunk, b_, ra, ta, p_), F)
+        accy = np.zeros_like(accx)
+        ca_prev = None
+        for n in range(n_):
+            ca, phi = draw(n)
+            ts =F(t0 + (1 if fault == "restart_t0_plus_1" else 0)) / fs
+            arg = (doppler * ts * ca + phi).astype(F)
+            ca_w = ca_prev if (fault == "w_prev" and ca_prev is not None) else ca
+            w = (doppler * (F(1) / fs) * ca_w).astype(F)
+            ca_prev = ca
+            sw, cw = np.sin(w), np.cos(w)
+            if fault == "no_reanchor" and t0 > 0:
+                vx, vy = chain[n]
+            else:
+                vx, vy = np.cos(arg), np.sin(arg)
+            vx, vy = np.broadcast_to(vx, accx.shape[1:]).astype(F), np.broadcast_to(vy, accx.shape[1:]).astype(F)
+            steps = kmax - 1 if (fault == "drop_last" and kmax < kchunk) else kmax
+            for k in range(kchunk if fault == "no_reanchor" else steps):
+                if k < steps:
+                    accx[k] = accx[k] + vx
+                    accy[k] = accy[k] + vy
+                vx, vy = (vx * cw + (-vy) * sw).astype(F), (vy * cw + vx * sw).astype(F)
+            if fault == "no_reanchor":
+                chain[n] = (vx, vy)
+        for k in range(kmax):
+            t = t0 + k
+            hx, hy = amp * (accx[k] * norm), amp * (accy[k] * norm)
+            if los:
+                cl = np.sin(F(los_aoa)) if fault == "los_sin" else np.cos(F(los_aoa))
+                arg = (doppler[..., 0] * (F(t) / fs) * F(cl) + phi0).astype(F)
+                kf = np.sqrt(F(los_power))
+                hx[..., p_los] = hx[..., p_los] + np.cos(arg) * kf
+                hy[..., p_los] = hy[..., p_los] + np.sin(arg) * kf
+            out[..., t] = hx + 1j * hy
+    return out[:, None, :, None]
+
+
+def cdl_cir_model(tables, seed, call, batch, num_time_steps, sampling_frequency, min_speed, max_speed, fault=None):
+    """Model of cdl_coupling_kernel + cdl_cir_kernel<float> in float32, operation for operation: ``tables`` are the float32 host
+    tables of ``CDL._host_tables()``; the ray indices go through ``perm`` (stable ranks of the four key streams), the field chain
+    is the kernel's expression, the rays are summed in ascending m, the LoS term last.  ``fault``: a seeded one-line fault
+    (tests/test_tap_channel_host.py).  -> complex64 [B, 1, U, 1, S, N, T]"""
+    from oracle import utils as outil
+    f_rx, f_tx, a_rx, a_tx, r_rx, pol_rx, pol_tx, order, amp, los, xpr_scale, k0 = tables
+    assert f_rx.dtype == F and a_rx.dtype == np.complex64
+    b_, t_, rays = int(batch), int(num_time_steps), 20
+    n_, u_, s_ = len(order), len(pol_rx), len(pol_tx)
+    fs, k0, kx = F(sampling_frequency), F(k0), F(xpr_scale)
+    if fault == "xpr_squared":
+        kx = kx * kx
+    v_r = _uni32(seed, call, b_, min_speed, max_speed)
+    v_phi = _uni32(seed, call + 1, b_, 0, F(2) * PI_F)
+    v_th = _uni32(seed, call + 2, b_, 0, PI_F)
+    vx, vy, vz = v_r * np.cos(v_phi) * np.sin(v_th), v_r * np.sin(v_phi) * np.sin(v_th), v_r * np.cos(v_th)
+    vx, vy, vz = (x.reshape(b_, 1) for x in (vx, vy, vz))
+    perm = []
+    for typ in range(4):                                                           # aoa, aod, zoa, zod
+        keys = np.stack(outil.philox_block(seed, call + 3 + typ, (b_ * n_ * rays + 3) // 4), axis=1).reshape(-1)[:b_ * n_ * rays]
+        perm.append(np.argsort(keys.reshape(b_, n_, rays), axis=-1, kind="stable"))
+    ph = _uni32(seed, call + 7, b_ * n_ * rays * 4, -PI_F, PI_F).reshape(b_, n_, rays, 4)
+    n_of = np.asarray(order)                                                       # cluster of output position no
+    bi = np.arange(b_)[:, None]
+    ps = np.zeros_like(pol_tx) if fault == "pol_tx_ignored" else pol_tx
+    ampn = amp[np.arange(n_)] if fault == "amp_unordered" else amp[n_of]          # [No]
+    ax = np.zeros((t_, b_, n_, u_, s_), F)
+    ay = np.zeros_like(ax)
+    tt = [F(t + (1 if fault == "time_plus_1" else 0)) / fs for t in range(t_)]
+
+    def rotate(hr, hi, w):
+        for t in range(t_):
+            arg = (w * tt[t])[:, :, None, None]
+            sn, cs = np.sin(arg), np.cos(arg)
+            ax[t] += hr * cs - hi * sn
+            ay[t] += hr * sn + hi * cs
+
+    for m in range(rays):
+        mz = (m + 1) % rays if fault == "zod_next_ray" else m
+        ia, ja = perm[0][bi, n_of, m], perm[1][bi, n_of, m]                         # [B, No]
+        iz, jz = perm[2][bi, n_of, m], perm[3][bi, n_of, mz]
+        fr = f_rx[n_of, iz, ia][:, :, pol_rx]                                      # [B, No, U, 2]
+        ft = f_tx[n_of, jz, ja][:, :, ps]                                          # [B, No, S, 2]
+        frt, frp = fr[..., 0][..., None], fr[..., 1][..., None]
+        ftt, ftp = ft[..., 0][:, :, None, :], ft[..., 1][:, :, None, :]
+        e4 = ph[bi, n_of, m]                                                       # [B, No, 4]
+        if fault == "phases_1_2_swapped":
+            e4 = e4[..., [0, 2, 1, 3]]
+        sn, cs = np.sin(e4)[:, :, None, None, :], np.cos(e4)[:, :, None, None, :]
+        cr = frt * (cs[..., 0] * ftt + kx * cs[..., 1] * ftp) + frp * (kx * cs[..., 2] * ftt + cs[..., 3] * ftp)
+        ci = frt * (sn[..., 0] * ftt + kx * sn[..., 1] * ftp) + frp * (kx * sn[..., 2] * ftt + sn[..., 3] * ftp)
+        ar = a_rx[n_of, iz, ia][..., None]                                         # [B, No, U, 1]
+        at = a_tx[n_of, jz, ja][:, :, None, :]
+        if fault == "a_tx_conj":
+            at = np.conj(at)
+        gr, gi = ar.real * at.real - ar.imag * at.imag, ar.real * at.imag + ar.imag * at.real
+        an = ampn[None, :, None, None]
+        hr, hi = (cr * gr - ci * gi) * an, (cr * gi + ci * gr) * an
+        rr = r_rx[n_of, jz, ja] if fault == "r_rx_departure" else r_rx[n_of, iz, ia]   # [B, No, 3]
+        w = k0 * (rr[..., 0] * vx + rr[..., 1] * vy + rr[..., 2] * vz)
+        rotate(hr, hi, w)
+    if los is not None:
+        frt, frp = los[0:4].reshape(2, 2)[pol_rx].T[:, :, None]                    # [U, 1] each
+        ftt, ftp = los[4:8].reshape(2, 2)[ps].T[:, None, :]                        # [1, S]
+        c = frt * ftt + frp * ftp if fault == "los_pm_identity" else frt * ftt - frp * ftp
+        ar = los[8:8 + 2 * u_].reshape(u_, 2)[:, None, :]
+        at = los[8 + 2 * u_:8 + 2 * u_ + 2 * s_].reshape(s_, 2)[None, :, :]
+        if fault == "a_tx_conj":
+            at = at * np.array([1, -1], F)
+        rr = los[8 + 2 * u_ + 2 * s_:]
+        kf = rr[3]
+        gr = (ar[..., 0] * at[..., 0] - ar[..., 1] * at[..., 1]) * c * kf
+        gi = (ar[..., 0] * at[..., 1] + ar[..., 1] * at[..., 0]) * c * kf
+        w = k0 * (rr[0] * vx + rr[1] * vy + rr[2] * vz)                             # [B, 1]
+        pos = 1 if fault == "los_position_1" else 0
+        for t in range(t_):
+            arg = (w * tt[t])[:, :, None]
+            sn, cs = np.sin(arg), np.cos(arg)
+            ax[t][:, pos] += gr * cs - gi * sn
+            ay[t][:, pos] += gr * sn + gi * cs
+    out = (ax + 1j * ay).astype(np.complex64)                                      # [T, B, No, U, S]
+    return np.ascontiguousarray(np.transpose(out, [1, 3, 4, 2, 0]))[:, None, :, None]
