@@ -1138,6 +1138,44 @@ int samd_pusch_ls_c128(const double* y, const int32_t* src, const double* coef, 
                        int64_t n_in, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Optical channels (csrc/optical.hip): channel/optical/fiber.py, channel/optical/edfa.py.  tests/optical_f32.py is the
+ * specification, DESIGN.md "Optical channels" states the noise rule and the bar.
+ *
+ * SSFM.call fiber.py:377-449 with _apply_linear_operator :257-282, _apply_noise :284-304, _apply_nonlinear_operator
+ * :306-326, _calculate_step_width / _adaptive_step / _cond_adaptive :329-354, _apply_window / _step :357-371 and the
+ * frequency vector of time_frequency_vector channel/utils.py:66-120.
+ * x, y [rows, n] complex (with_manakov: [rows, 2, n], both polarisations of a sample rotate by 8/9 of their summed power);
+ * y may be x.  n_ssfm > 0: the symmetric scheme of :425-447 with dz = length / n_ssfm; n_ssfm = -1: the adaptive step
+ * width of :414-422, dz = min(phase_inc / gamma / max|q|^2, remaining) found on the device, until remaining < 1e-3.
+ * The transforms are rocFFT's, batched over rows (x 2), any n; with_dispersion = 0 runs none.  The window is the Hamming
+ * taper 0.54 - 0.46 cos(2 pi k / (2 h)) in the first and last h = half_window_length samples, 2 h <= n.
+ * with_amplification: the Raman gain exp(alpha dz / 2) per step and ASE noise of variance p_n_ase dz / length / 2 per
+ * real dimension (p_n_ase as in :236-244, from the caller).  Noise: element i of the flattened tensor takes half i & 1
+ * of Philox block i / 2 of the stream (seed, call + s) in step s, Box-Muller as in samd_awgn_c64 (_c128: the same 24-bit
+ * uniforms, evaluated in double).  *steps (HOST) receives the number of steps taken, i.e. of call values consumed.
+ * workspace: DEVICE, samd_ssfm_workspace_bytes(n, double_precision) bytes.  The adaptive scheme reads the remaining
+ * length back once per step (a stream synchronisation); both schemes synchronise once after uploading their tables. */
+size_t samd_ssfm_workspace_bytes(int n, int double_precision);
+int samd_ssfm_c64(const float* x, int64_t rows, int n, int with_manakov, double alpha, double beta_2, double gamma,
+                  double length, double sample_duration, int n_ssfm, double phase_inc, int half_window_length,
+                  double p_n_ase, int with_amplification, int with_attenuation, int with_dispersion,
+                  int with_nonlinearity, uint64_t seed, uint64_t call, int64_t* steps, void* workspace,
+                  size_t workspace_bytes, float* y, void* stream);
+int samd_ssfm_c128(const double* x, int64_t rows, int n, int with_manakov, double alpha, double beta_2, double gamma,
+                   double length, double sample_duration, int n_ssfm, double phase_inc, int half_window_length,
+                   double p_n_ase, int with_amplification, int with_attenuation, int with_dispersion,
+                   int with_nonlinearity, uint64_t seed, uint64_t call, int64_t* steps, void* workspace,
+                   size_t workspace_bytes, double* y, void* stream);
+
+/* EDFA.call edfa.py:145-170 in one streaming launch: y = sqrt_g x + sigma (w_re + j w_im), x, y complex[n] (y may be x);
+ * sqrt_g = sqrt(g) and sigma = sqrt(p_n_ase / 2) (:126-143, halved power with dual polarisation) from the caller;
+ * sigma = 0 draws nothing.  Element i takes half i & 1 of Philox block i / 2 of (seed, call). */
+int samd_edfa_c64(const float* x, int64_t n, double sqrt_g, double sigma, uint64_t seed, uint64_t call, float* y,
+                  void* stream);
+int samd_edfa_c128(const double* x, int64_t n, double sqrt_g, double sigma, uint64_t seed, uint64_t call, double* y,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Error counting  utils/metrics.py:94-144 (count_errors, count_block_errors).
  * b, b_hat [num_blocks, block_len] float32; counters: DEVICE int64[2], ADDED to:
  * counters[0] += #(b != b_hat), counters[1] += #blocks with any mismatch.

@@ -142,6 +142,10 @@ _SIGNATURES = {
     "samd_rg_map_c64": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     **{f"samd_discrete_channel_{t}": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _f64, _u64, _u64, _i64, _vp, _vp])
        for t in ("f32", "f64", "i8", "u8", "i16", "i32", "i64")},
+    "samd_ssfm_workspace_bytes": (_sz, [_i32, _i32]),
+    **{f"samd_ssfm_{t}": (_i32, [_vp, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _f64, _i32, _f64, _i32, _f64, _i32, _i32, _i32,
+                                 _i32, _u64, _u64, C.POINTER(_i64), _vp, _sz, _vp, _vp]) for t in ("c64", "c128")},
+    **{f"samd_edfa_{t}": (_i32, [_vp, _i64, _f64, _f64, _u64, _u64, _vp, _vp]) for t in ("c64", "c128")},
     "samd_gather3": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "samd_tdl_cir_c64": (_i32, [_u64, _u64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _f32, _f32, _i32, _f32,
                                 _f32, _vp, _vp]),

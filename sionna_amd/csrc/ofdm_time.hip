@@ -14,6 +14,7 @@
 // insertion / removal, the 1/sqrt(N) scaling and the l_min phase compensation are folded into
 // one gather pass before and one scatter pass after the transform.
 #include "common.h"
+#include "rocfft_plan.h"
 
 #include <dlfcn.h>
 #include <rocfft/rocfft.h>
@@ -91,8 +92,11 @@ bool load_rocfft_locked() {
   return true;
 }
 
-// Batched in-place 1-D complex64 (dbl: complex128) transform of `batch` contiguous rows of length n.
-int fft_inplace(void* data, int n, int batch, bool inverse, hipStream_t stream, bool dbl = false) {
+}  // namespace
+
+// Batched in-place 1-D complex64 (dbl: complex128) transform of `batch` contiguous rows of length n (rocfft_plan.h:
+// shared with optical.hip).
+int fft_inplace(void* data, int n, int batch, bool inverse, hipStream_t stream, bool dbl) {
   std::lock_guard<std::mutex> lock(g_fft_mutex);
   if (!load_rocfft_locked()) {
     set_error(g_fft.err);
@@ -135,6 +139,8 @@ int fft_inplace(void* data, int n, int batch, bool inverse, hipStream_t stream, 
   }
   return SAMD_OK;
 }
+
+namespace {
 
 // ---------------------------------------------------------------- kernels
 // work[r, s, k] = x[r, s, (k + n/2 [ceil for ifftshift]) mod n]: ifftshift moves the DC

@@ -1,7 +1,9 @@
 """Channel models of the hot path (mirror of ``sionna.phy.channel``)."""
 from .awgn import AWGN
 from .discrete_channel import BinaryMemorylessChannel, BinarySymmetricChannel, BinaryZChannel, BinaryErasureChannel
-from .utils import subcarrier_frequencies, cir_to_ofdm_channel, time_to_ofdm_channel
+from .utils import subcarrier_frequencies, cir_to_ofdm_channel, time_to_ofdm_channel, time_frequency_vector
+from . import optical
+from .optical import SSFM, EDFA
 from .ofdm_channel import GenerateOFDMChannel, ApplyOFDMChannel, OFDMChannel, RayleighBlockFading
 from .time_channel import (time_lag_discrete_time_channel, cir_to_time_channel, GenerateTimeChannel,
                            ApplyTimeChannel, TimeChannel)

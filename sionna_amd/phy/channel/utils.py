@@ -17,6 +17,18 @@ def subcarrier_frequencies(num_subcarriers, subcarrier_spacing, precision=None):
     return (np.arange(start, limit, dtype=f) * f(subcarrier_spacing)).astype(f)
 
 
+def time_frequency_vector(num_samples, sample_duration, precision=None):
+    """Time and frequency vector of ``num_samples`` samples of ``sample_duration`` (normalised time), both ascending with
+    the zero at index num_samples // 2 (utils.py:66-120): t = k sample_duration, f = k / (sample_duration num_samples),
+    k = -(num_samples // 2) ... (num_samples - 1) // 2, each product rounded once in the precision's real type."""
+    p = config.precision if precision is None else precision
+    r = dtypes[p]["np"]["rdtype"]
+    num_samples = int(num_samples)
+    k = np.arange(-(num_samples // 2), (num_samples + 1) // 2, dtype=np.int32).astype(r)
+    df = r(r(1.0 / sample_duration) / r(num_samples))
+    return (k * r(sample_duration)).astype(r), (k * df).astype(r)
+
+
 def cir_to_ofdm_channel(frequencies, a, tau, normalize=False):
     """h_f[b,rx,ra,tx,ta,t,f] = sum_p a[b,rx,ra,tx,ta,p,t] exp(-j 2 pi f tau[b,rx,tx,p])
     (+ optional normalisation to unit mean energy per (b,rx,tx)) - utils.py:180-253."""

@@ -598,6 +598,23 @@ def make_tf():
         return _t((lo + (hi - lo) * g.random([int(v) for v in np.atleast_1d(shape)])).astype(dtype._np if isinstance(dtype, DType) else dtype))
     tf.random = types.SimpleNamespace(Generator=_Generator, stateless_uniform=_stateless_uniform)
     tf.assert_equal = tf.debugging.assert_equal
+    # ---- ops of the optical channels (channel/optical/fiber.py)
+    def _assert_greater(x, y, message=None, **k):
+        if not np.all(np.asarray(x) > np.asarray(y)):
+            raise AssertionError(message or "assert_greater")
+    tf.assert_greater = _assert_greater
+    def _hamming_window(window_length, periodic=True, dtype=np.float32, name=None):
+        """tf.signal.hamming_window (window_ops.py _raised_cosine_window): a - b cos(2 pi k / (N + periodic * even - 1)),
+        evaluated in ``dtype``"""
+        dt = np.dtype(dtype._np if isinstance(dtype, DType) else dtype).type
+        length = int(window_length)
+        if length == 1:
+            return _t(np.ones(1, dt))
+        even = 1 - length % 2
+        denom = dt(length + int(bool(periodic)) * even - 1)
+        arg = dt(2.0 * np.pi) * np.arange(length).astype(dt) / denom
+        return _t((dt(0.54) - dt(0.46) * np.cos(arg)).astype(dt))
+    tf.signal.hamming_window = _hamming_window
     tf.name_scope = lambda *a, **k: _NullCtx()
     class Variable(Tensor):
         """tf.Variable stand-in (an ndarray view; ``isinstance(x, tf.Variable)`` is False for plain tensors)."""
