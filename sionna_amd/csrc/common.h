@@ -99,6 +99,14 @@ inline int set_max_dynamic_lds(const void* fn, int bytes) {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// compute units of the current device; an MI355X's 256 where the query fails
+inline int device_cus() {
+  int dev = 0, cus = 256;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus;
+}
+
 constexpr int kWave = 64;  // CDNA wavefront
 
 // ---------------------------------------------------------------- device helpers

@@ -196,6 +196,31 @@ struct samd_ldpc5g {
 
 namespace samd {
 
+// ---- launch-side rules the engines share
+// base columns that hold at least one un-pruned node
+inline int used_cols(const samd_ldpc5g* h) { return (h->n_vn + h->z - 1) / h->z; }
+
+// workgroups of `waves` waves a CU holds: kDecWaves waves in all, 160 KB of LDS
+inline size_t onchip_wgs_per_cu(int waves, size_t lds_bytes) {
+  return std::min<size_t>((size_t)(kDecWaves / waves), std::max<size_t>(1, (160 * 1024) / lds_bytes));
+}
+
+// the count-based duplicate-minimum test of the min-sum kernels equals the reference's 1e5-sentinel sum test only
+// while node_degree * 2 * llr_max stays below the sentinel (decoding.py:865-872)
+inline bool minsum_envelope_ok(const samd_ldpc5g* h, float llr_max) {
+  return h->max_dc <= 27 && llr_max >= 0.f && !((double)h->max_dc * 2.0 * (double)llr_max >= 99999.0);
+}
+
+// the caller's workspace of samd_ldpc5g_decode_f32, held to `need` bytes: *base = its first 256-byte boundary
+inline int decode_workspace(void* workspace, size_t workspace_bytes, size_t need, float** base) {
+  if (!workspace || workspace_bytes < need) {
+    set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
+    return SAMD_ERR_WORKSPACE;
+  }
+  *base = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
+  return SAMD_OK;
+}
+
 // longest-processing-time-first assignment of items to the waves of the workgroup: an item goes to the wave whose load
 // is smallest after taking it (the first such wave).
 inline void lpt_schedule(const std::vector<std::pair<int, int32_t>>& items, int nw, std::vector<int32_t>* ptr,

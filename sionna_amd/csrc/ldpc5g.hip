@@ -357,10 +357,6 @@ __global__ __launch_bounds__(kDecThreads) void ldpc5g_decode_kernel(
   }
 }
 
-static RateMatch make_rm(const samd_ldpc5g* h) {
-  return make_rate_match(h);
-}
-
 static size_t decode_lds_bytes(const samd_ldpc5g* h) {
   return ((size_t)2 * h->n_vn + (size_t)3 * h->n_cn) * 4 + 16;
 }
@@ -490,14 +486,14 @@ extern "C" int samd_ldpc5g_encode_f32(const samd_ldpc5g_t* h, const float* bits,
     // stores before the next input arrives (loads and stores share the in-order vmcnt counter) - measured 1.12 ms
     // against 0.28 ms (input + rows) + 0.42 ms (output) for the separate phases at C2
     const int grid = (batch + 3) / 4;
-    hipLaunchKernelGGL(ldpc5g_encode_packed_kernel, dim3(grid), dim3(256), lds_p, (hipStream_t)stream, bits, out, make_rm(h),
+    hipLaunchKernelGGL(ldpc5g_encode_packed_kernel, dim3(grid), dim3(256), lds_p, (hipStream_t)stream, bits, out, make_rate_match(h),
                        batch, h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->base.row_ptr.get(), h->base.row_ent.get(),
                        h->base.enc_out_idx.get(), h->opt.enc_dbg);
     return launch_status();
   }
   const size_t lds = (size_t)h->n_ldpc + 4 * (size_t)h->z;
   SAMD_SET_MAX_LDS(ldpc5g_encode_kernel, 64 * 1024);
-  hipLaunchKernelGGL(ldpc5g_encode_kernel, dim3(batch), dim3(256), lds, (hipStream_t)stream, bits, out, make_rm(h),
+  hipLaunchKernelGGL(ldpc5g_encode_kernel, dim3(batch), dim3(256), lds, (hipStream_t)stream, bits, out, make_rate_match(h),
                      h->mb, h->k_b, h->bg, h->s_a, h->s_b, h->base.row_ptr.get(), h->base.row_ent.get());
   return launch_status();
 }
@@ -508,7 +504,7 @@ extern "C" int samd_ldpc5g_rate_recover_f32(const samd_ldpc5g_t* h, const float*
   for (int b0 = 0; b0 < batch; b0 += 65535) {
     const int nb = std::min(65535, batch - b0);
     hipLaunchKernelGGL(ldpc5g_rate_recover_kernel, dim3((h->n_vn + 255) / 256, nb), dim3(256), 0, (hipStream_t)stream,
-                       llr + (size_t)b0 * h->n, out + (size_t)b0 * h->n_vn, make_rm(h), llr_max);
+                       llr + (size_t)b0 * h->n, out + (size_t)b0 * h->n_vn, make_rate_match(h), llr_max);
   }
   return launch_status();
 }
@@ -519,7 +515,7 @@ extern "C" int samd_ldpc5g_extract_codeword_f32(const samd_ldpc5g_t* h, const fl
   for (int b0 = 0; b0 < batch; b0 += 65535) {
     const int nb = std::min(65535, batch - b0);
     hipLaunchKernelGGL(ldpc5g_extract_kernel, dim3((h->n + 255) / 256, nb), dim3(256), 0, (hipStream_t)stream,
-                       x_hat + (size_t)b0 * h->n_vn, out + (size_t)b0 * h->n, make_rm(h));
+                       x_hat + (size_t)b0 * h->n_vn, out + (size_t)b0 * h->n, make_rate_match(h));
   }
   return launch_status();
 }
@@ -562,12 +558,6 @@ static EngineList decode_engines(const samd_ldpc5g* h, int cn_mode) {
   if (h->v2.ok) l.add(kEngV2);                             // statically scheduled, unrolled (every 5G code)
   if (decode_lds_bytes(h) <= 160 * 1024) l.add(kEngFirst);
   return l;
-}
-
-// the count-based duplicate-minimum test of the min-sum kernels equals the reference's 1e5-sentinel sum test only
-// while node_degree * 2 * llr_max stays below the sentinel (decoding.py:865-872)
-static bool minsum_envelope_ok(const samd_ldpc5g* h, float llr_max) {
-  return h->max_dc <= 27 && llr_max >= 0.f && !((double)h->max_dc * 2.0 * (double)llr_max >= 99999.0);
 }
 
 extern "C" size_t samd_ldpc5g_decode_workspace_bytes(const samd_ldpc5g_t* h, int batch, int cn_mode) {
@@ -657,13 +647,10 @@ static int launch_onchip_first(const samd_ldpc5g* h, const float* llr, float* ou
   const bool off = (cn_mode == SAMD_CN_OFFSET_MINSUM);
   const void* fn = off ? (const void*)ldpc5g_decode_kernel<true> : (const void*)ldpc5g_decode_kernel<false>;
   SAMD_SET_MAX_LDS(fn, 160 * 1024);
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const size_t per_cu = std::max<size_t>(1, (160 * 1024) / lds);
-  const int grid = (int)std::min<size_t>((size_t)batch, (size_t)cus * std::min<size_t>(per_cu, 2));
+  const int grid = (int)std::min<size_t>((size_t)batch, (size_t)device_cus() * std::min<size_t>(per_cu, 2));
   const float off_v = off ? offset : 0.f;
-#define SAMD_DEC_ARGS llr, out, make_rm(h), h->n_cn, batch, num_iter, llr_max, off_v, hard_out, return_infobits, \
+#define SAMD_DEC_ARGS llr, out, make_rate_match(h), h->n_cn, batch, num_iter, llr_max, off_v, hard_out, return_infobits, \
                       h->base.row_ptr.get(), h->base.row_ent.get(), h->base.col_ptr.get(), h->base.col_ent.get(), \
                       h->base.cn_items.get(), h->base.n_cn_items, h->base.vn_items.get(), h->base.n_vn_items
   if (off) hipLaunchKernelGGL(ldpc5g_decode_kernel<true>, dim3(grid), dim3(kDecThreads), lds, stream, SAMD_DEC_ARGS);

@@ -82,12 +82,10 @@ static hipFunction_t get_function(const samd_ldpc5g* h, Compiled* c, int vi, int
 }
 
 // grid of the generated kernel for `batch` codewords (group codewords per workgroup, wgs workgroups per CU; 0: onchip_bp_grid)
-static int jit_grid(const samd_ldpc5g* h, int batch, int group, int wgs, int dev) {
+static int jit_grid(const samd_ldpc5g* h, int batch, int group, int wgs) {
   if (wgs <= 0) return onchip_bp_grid(h, batch);
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const int ngroups = (batch + group - 1) / group;
-  int grid = std::min(ngroups, cus * wgs);
+  int grid = std::min(ngroups, device_cus() * wgs);
   if (h->opt.onchip_grid > 0) grid = std::min(grid, h->opt.onchip_grid);
   return grid;
 }
@@ -99,9 +97,7 @@ size_t jit_workspace_bytes(const samd_ldpc5g* h, int batch, int cn_mode) {
   if (jit_class(h, phi) != 2) return 0;
   JitGeometry g;
   if (!jit_geometry(h, phi, &g) || g.ws_bytes == 0) return 0;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return (size_t)jit_grid(h, batch, g.pairx ? 2 * g.G : g.G, g.wgs, dev) * g.ws_bytes + 256;
+  return (size_t)jit_grid(h, batch, g.pairx ? 2 * g.G : g.G, g.wgs) * g.ws_bytes + 256;
 }
 
 int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
@@ -136,7 +132,7 @@ int launch_onchip_jit(const samd_ldpc5g* h, const float* llr, float* out, int ba
     return SAMD_ERR_UNSUPPORTED;
   }
   float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
-  const int grid = jit_grid(h, batch, c->prog.group, c->prog.wgs, dev);
+  const int grid = jit_grid(h, batch, c->prog.group, c->prog.wgs);
   float* ws = nullptr;
   if (c->prog.ws_bytes) {                                           // the last base rows' messages: a row per workgroup, caller-owned
     const size_t need = (size_t)grid * c->prog.ws_bytes + 256;

@@ -20,7 +20,7 @@
 // LDS per codeword: xt[nbu*Z] + llr[nbu*Z] floats, check-node state float2 m12[(ncu+1)*Z]
 // + uint pk[(ncu+1)*Z] (the extra block is the dummy CN): 141.8 KB for C2 -> 1 workgroup
 // (16 waves) per CU.
-#include "ldpc5g.h"
+#include "ldpc5g_io.h"
 
 #include <algorithm>
 #include <numeric>
@@ -243,9 +243,7 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_v2_kernel(
   for (int b = blockIdx.x; b < batch; b += gridDim.x) {
     const float* row = llr_in + (size_t)b * p.n;
     for (int v = tid; v < nx; v += NT) {
-      // decoding.py:552-565: clip, then logits -> LLR; "+ 0.f" turns -0 into +0 (numerically the
-      // same LLR) so that the sign bit of every later v2c equals (v2c < 0)
-      const float l = (v < n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
+      const float l = channel_llr<true>(p, row, v, n_vn, llr_max);
       llr[v] = l;
       xt[v] = l;
     }
@@ -300,20 +298,8 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_v2_kernel(
       }
       __syncthreads();
     }
-    // ---------------- output (decoding.py:620-626, 1486-1531)
-    if (return_infobits) {
-      float* o = out + (size_t)b * p.k;
-      for (int v = tid; v < p.k; v += NT) {
-        const float x = clampf(xt[v], -llr_max, llr_max);
-        o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    } else {
-      float* o = out + (size_t)b * p.n;
-      for (int i = tid; i < p.n; i += NT) {
-        const float x = clampf(xt[short_to_full(p, out_to_short(p, i))], -llr_max, llr_max);
-        o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    }
+    store_codeword(p, out, (size_t)b, [&](int v) { return xt[v]; }, llr_max, hard_out,
+                   return_infobits, tid, NT);
     __syncthreads();
   }
 }
@@ -439,11 +425,7 @@ static size_t onchip_lds_bytes(const samd_ldpc5g* h) {
 }
 
 static int onchip_grid(const samd_ldpc5g* h, int batch) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t per_cu = std::min<size_t>((size_t)(kDecWaves / h->v2.dec_waves), std::max<size_t>(1, (160 * 1024) / onchip_lds_bytes(h)));
-  return (int)std::min<size_t>((size_t)batch, (size_t)cus * per_cu);
+  return (int)std::min<size_t>((size_t)batch, (size_t)device_cus() * onchip_wgs_per_cu(h->v2.dec_waves, onchip_lds_bytes(h)));
 }
 
 size_t onchip_workspace_bytes(const samd_ldpc5g* h, int batch) {
@@ -462,11 +444,8 @@ int launch_onchip_v2(const samd_ldpc5g* h, const float* llr, float* out, int bat
   }
   float* llr_ws = nullptr;
   if (h->v2.llr_global) {
-    if (!workspace || workspace_bytes < onchip_workspace_bytes(h, batch)) {
-      set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
-      return SAMD_ERR_WORKSPACE;
-    }
-    llr_ws = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
+    const int rc = decode_workspace(workspace, workspace_bytes, onchip_workspace_bytes(h, batch), &llr_ws);
+    if (rc != SAMD_OK) return rc;
   }
   const bool off = (cn_mode == SAMD_CN_OFFSET_MINSUM);
   const bool pow2 = (h->z & (h->z - 1)) == 0;

@@ -18,7 +18,7 @@
 // Work split: (row, 64-lane chunk) and (column, chunk) items are assigned to the waves on the host
 // (longest-processing-time first); every item is an instantiation for the row's exact degree / the
 // column's degree class, all table entries are wave-uniform scalars.
-#include "ldpc5g.h"
+#include "ldpc5g_io.h"
 #include "ldpc5g_jit.h"
 
 #include <cmath>
@@ -109,9 +109,7 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_bp_kernel(
 
   for (int b = blockIdx.x; b < batch; b += gridDim.x) {
     const float* row = llr_in + (size_t)b * p.n;
-    // decoding.py:552-565: clip, then logits -> LLR
-    for (int v = tid; v < nx; v += NT)
-      llr[v] = (v < n_vn) ? -1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max) : 0.f;
+    for (int v = tid; v < nx; v += NT) llr[v] = channel_llr<false>(p, row, v, n_vn, llr_max);
     __syncthreads();
     for (int t = v0; t < v1; ++t) {                                // v2c of iteration 0
       const int desc = __builtin_amdgcn_readfirstlane(vn_list[t]);  // c | chunk<<8
@@ -162,20 +160,9 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_bp_kernel(
       }
       __syncthreads();
     }
-    // ---------------- output (decoding.py:620-626, 1486-1531); llr[] now holds the marginals
-    if (return_infobits) {
-      float* o = out + (size_t)b * p.k;
-      for (int v = tid; v < p.k; v += NT) {
-        const float x = clampf(llr[v], -llr_max, llr_max);
-        o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    } else {
-      float* o = out + (size_t)b * p.n;
-      for (int i = tid; i < p.n; i += NT) {
-        const float x = clampf(llr[short_to_full(p, out_to_short(p, i))], -llr_max, llr_max);
-        o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    }
+    // llr[] now holds the marginals
+    store_codeword(p, out, (size_t)b, [&](int v) { return llr[v]; }, llr_max, hard_out,
+                   return_infobits, tid, NT);
     __syncthreads();
   }
 }
@@ -637,16 +624,11 @@ int build_onchip_bp_tables(samd_ldpc5g* h, const BaseRows& by_row) {
 }
 
 size_t onchip_bp_lds_bytes(const samd_ldpc5g* h) {
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)h->bp.edges * h->z * 4 + (h->bp.llr_global ? 0 : (size_t)nbu * h->z * 4);
+  return (size_t)h->bp.edges * h->z * 4 + (h->bp.llr_global ? 0 : (size_t)used_cols(h) * h->z * 4);
 }
 
 int onchip_bp_grid(const samd_ldpc5g* h, int batch) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t per_cu = std::min<size_t>((size_t)(kDecWaves / h->bp.waves), std::max<size_t>(1, (160 * 1024) / onchip_bp_lds_bytes(h)));
-  size_t grid = std::min<size_t>((size_t)batch, (size_t)cus * per_cu);
+  size_t grid = std::min<size_t>((size_t)batch, (size_t)device_cus() * onchip_wgs_per_cu(h->bp.waves, onchip_bp_lds_bytes(h)));
   // SAMD_ONCHIP_GRID=<n>: fewer workgroups than the chip holds (test hook: every workgroup then decodes several
   // codewords in sequence, which exercises the grid-stride loop and the reuse of its workspace row on small batches)
   if (h->opt.onchip_grid > 0) grid = std::min<size_t>(grid, (size_t)h->opt.onchip_grid);
@@ -655,8 +637,7 @@ int onchip_bp_grid(const samd_ldpc5g* h, int batch) {
 
 size_t onchip_bp_workspace_bytes(const samd_ldpc5g* h, int batch) {
   if (!h->bp.ok || !h->bp.llr_global || batch <= 0) return 0;
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)onchip_bp_grid(h, batch) * nbu * h->z * sizeof(float) + 256;
+  return (size_t)onchip_bp_grid(h, batch) * used_cols(h) * h->z * sizeof(float) + 256;
 }
 
 int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
@@ -668,11 +649,8 @@ int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int bat
   }
   float* llr_ws = nullptr;
   if (h->bp.llr_global) {
-    if (!workspace || workspace_bytes < onchip_bp_workspace_bytes(h, batch)) {
-      set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
-      return SAMD_ERR_WORKSPACE;
-    }
-    llr_ws = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
+    const int rc = decode_workspace(workspace, workspace_bytes, onchip_bp_workspace_bytes(h, batch), &llr_ws);
+    if (rc != SAMD_OK) return rc;
   }
   const bool pow2 = (h->z & (h->z - 1)) == 0;
   const bool phi = (cn_mode == SAMD_CN_BOXPLUS_PHI);
@@ -693,10 +671,9 @@ int launch_onchip_bp(const samd_ldpc5g* h, const float* llr, float* out, int bat
   const int ki = (phi ? 0 : 12) + 2 * wi + (pow2 ? 1 : 0);
   // set on every launch: the attribute is per device and a process may drive several
   SAMD_SET_MAX_LDS(kerns[ki], 160 * 1024);
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
   const RateMatch rm = make_rate_match(h);
   hipLaunchKernelGGL(kerns[ki], dim3(onchip_bp_grid(h, batch)), dim3(nw * 64), onchip_bp_lds_bytes(h), st, llr, out, llr_ws, rm,
-                     h->n_cn, nbu, batch, num_iter, llr_max, hard_out, return_infobits, h->bp.edges * h->z,
+                     h->n_cn, used_cols(h), batch, num_iter, llr_max, hard_out, return_infobits, h->bp.edges * h->z,
                      h->bp.row_off.get(), h->bp.col_ent.get(), h->bp.col_deg.get(), h->bp.cn_ptr.get(), h->bp.cn_list.get(),
                      h->bp.vn_ptr.get(), h->bp.vn_list.get());
   return launch_status();

@@ -263,11 +263,8 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_ly_kernel(
     // are they written to the workspace row: until round 4 every LLR went through it (and every final fused c2v), 45 KB
     // per codeword written and read back through L2 - 6.7 GB per launch at C2 on the memory-side counters against
     // 2.95 GB of compulsory input + output (profiles/r03zy_pmc).
-    auto chan_llr = [&](int v) __attribute__((always_inline)) -> float {
-      return (v < p.n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
-    };
     for (int v = tid; v < nx; v += NT) {
-      const float l = chan_llr(v);
+      const float l = channel_llr<true>(p, row, v, p.n_vn, llr_max);
       const int xi = xt_index[v / (int)z];
       if (xi >= 0) xtot[xi * (int)z + v % (int)z] = l;                 // total of a node without messages = its LLR
       else if (!return_infobits) llr[v] = l;
@@ -280,7 +277,8 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_ly_kernel(
     for (int q = 0; q < LY_CN_SLOTS; ++q) {
       const int li = slots[q];
       st[LY_ST_CO + q] = 0.f;
-      st[LY_ST_LF + q] = (li >= 0) ? chan_llr(min(li + lane, nx - 1)) : 0.f;   // (lanes past a partial chunk: never used)
+      // (lanes past a partial chunk: never used)
+      st[LY_ST_LF + q] = (li >= 0) ? channel_llr<true>(p, row, min(li + lane, nx - 1), p.n_vn, llr_max) : 0.f;
     }
     for (int i = tid; i < msg_floats; i += NT) smem[i] = 0.f;
     for (int i = tid; i < (int)z; i += NT) smem[zero_off + i] = 0.f;   // the block the padded re-sum entries read
@@ -393,19 +391,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_ly_kernel(
       if (xi == -0x7FFFFFFF) return llr[v];                              // column without edges in the pruned graph
       return cext[(-1 - xi) * (int)z + zv] + llr[v];
     };
-    if (return_infobits) {
-      float* o = out + (size_t)b * p.k;
-      for (int v = tid; v < p.k; v += NT) {
-        const float x = clampf(marginal(v), -llr_max, llr_max);
-        o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    } else {
-      float* o = out + (size_t)b * p.n;
-      for (int i = tid; i < p.n; i += NT) {
-        const float x = clampf(marginal(short_to_full(p, out_to_short(p, i))), -llr_max, llr_max);
-        o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    }
+    store_codeword(p, out, (size_t)b, marginal, llr_max, hard_out, return_infobits, tid, NT);
     __syncthreads();
   }
 }
@@ -834,18 +820,14 @@ int build_onchip_ly_tables(samd_ldpc5g* h, const BaseRows& by_row) {
 }
 
 static int ly_grid(const samd_ldpc5g* h, int batch) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  int grid = std::min(batch, cus * (16 / std::max(4, h->ly.waves)));
+  int grid = std::min(batch, device_cus() * (16 / std::max(4, h->ly.waves)));
   if (h->opt.onchip_grid > 0) grid = std::min(grid, h->opt.onchip_grid);
   return grid;
 }
 
 size_t onchip_ly_workspace_bytes(const samd_ldpc5g* h, int batch) {
   if (!h->ly.ok || batch <= 0) return 0;
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)ly_grid(h, batch) * (size_t)(nbu + h->ly.n_ext) * h->z * sizeof(float) + 256;
+  return (size_t)ly_grid(h, batch) * (size_t)(used_cols(h) + h->ly.n_ext) * h->z * sizeof(float) + 256;
 }
 
 int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode, float llr_max,
@@ -856,7 +838,7 @@ int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int bat
     set_error("layered on-chip engine: code or rule not covered (the HBM-resident scheduled engine takes it)");
     return SAMD_ERR_UNSUPPORTED;
   }
-  if (minsum && (h->max_dc > 27 || !(llr_max >= 0.f) || (double)h->max_dc * 2.0 * (double)llr_max >= 99999.0)) {
+  if (minsum && !minsum_envelope_ok(h, llr_max)) {
     set_error("code / llr_max outside the on-chip decoder's envelope");
     return SAMD_ERR_UNSUPPORTED;
   }
@@ -874,14 +856,13 @@ int launch_onchip_ly(const samd_ldpc5g* h, const float* llr, float* out, int bat
 #undef SAMD_LY_K
   const kern_t fn = kerns[minsum ? 0 : cn_mode == SAMD_CN_BOXPLUS_PHI ? 1 : 2][h->z % 64 != 0 ? 1 : 0][pow2 ? 1 : 0];
   SAMD_SET_MAX_LDS(fn, 160 * 1024);
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
   const RateMatch rm = make_rate_match(h);
   const float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
   // the boxplus rules walk the lists with split check-node items where the code has them (more LDS: the parts' scratch)
   const bool parts = !minsum && h->ly.bp_lds_bytes > 0;
   const samd::Ldpc5gLayered& t = h->ly;
   hipLaunchKernelGGL(fn, dim3(ly_grid(h, batch)), dim3(64 * t.waves), (size_t)(parts ? t.bp_lds_bytes : t.lds_bytes), st,
-                     llr, out, ws, rm, nbu, batch, num_iter, llr_max, off, hard_out, return_infobits, t.msg_floats, t.n_ext,
+                     llr, out, ws, rm, used_cols(h), batch, num_iter, llr_max, off, hard_out, return_infobits, t.msg_floats, t.n_ext,
                      t.zero_off, 64 * t.waves, parts ? t.bp_rec_ptr.get() : t.rec_ptr.get(),
                      reinterpret_cast<const int4*>(parts ? t.bp_recs.get() : t.recs.get()), t.ent_tab.get(),
                      t.xt_index.get(), parts ? t.bp_slot_tab.get() : t.slot_tab.get());

@@ -103,8 +103,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_lyrt_kernel(
     for (int s = 0; s < live; ++s) {
       float* blk = smem + (size_t)s * slot_floats;
       const float* row = llr_in + (size_t)(b0 + s) * p.n;
-      for (int v = tid; v < nx; v += NT)
-        blk[v] = (v < p.n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
+      for (int v = tid; v < nx; v += NT) blk[v] = channel_llr<true>(p, row, v, p.n_vn, llr_max);
       for (int i = tid; i < nrec; i += NT) blk[nx + i] = 0.f;
     }
     __syncthreads();
@@ -142,19 +141,8 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_lyrt_kernel(
     // ---------------- output (decoding.py:620-626, 1486-1531): blk[] holds the marginals
     for (int s = 0; s < live; ++s) {
       const float* blk = smem + (size_t)s * slot_floats;
-      if (return_infobits) {
-        float* o = out + (size_t)(b0 + s) * p.k;
-        for (int v = tid; v < p.k; v += NT) {
-          const float x = clampf(blk[v], -llr_max, llr_max);
-          o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-        }
-      } else {
-        float* o = out + (size_t)(b0 + s) * p.n;
-        for (int i = tid; i < p.n; i += NT) {
-          const float x = clampf(blk[short_to_full(p, out_to_short(p, i))], -llr_max, llr_max);
-          o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-        }
-      }
+      store_codeword(p, out, (size_t)(b0 + s), [&](int v) { return blk[v]; }, llr_max,
+                     hard_out, return_infobits, tid, NT);
     }
     __syncthreads();
   }
@@ -244,17 +232,14 @@ int launch_onchip_lyrt(const samd_ldpc5g* h, const float* llr, float* out, int b
     set_error("layered running-total engine: code or rule not covered");
     return SAMD_ERR_UNSUPPORTED;
   }
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  int grid = std::min((batch + t.slots - 1) / t.slots, cus * t.wg_per_cu);
+  int grid = std::min((batch + t.slots - 1) / t.slots, device_cus() * t.wg_per_cu);
   if (h->opt.onchip_grid > 0) grid = std::min(grid, h->opt.onchip_grid);
   const bool pow2 = (h->z & (h->z - 1)) == 0;
   typedef void (*kern_t)(const float*, float*, RateMatch, int, int, int, int, float, float, int, int, int, int, int,
                          const int32_t*, const int4*, const int32_t*);
   const kern_t fn = pow2 ? ldpc5g_decode_lyrt_kernel<true> : ldpc5g_decode_lyrt_kernel<false>;
   SAMD_SET_MAX_LDS(fn, 160 * 1024);
-  const int nbu = (h->n_vn + h->z - 1) / h->z, ncu = (h->n_cn + h->z - 1) / h->z;
+  const int nbu = used_cols(h), ncu = (h->n_cn + h->z - 1) / h->z;
   const float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * t.waves), (size_t)t.slots * (size_t)t.slot_bytes, st, llr, out,
                      make_rate_match(h), nbu, ncu, batch, num_iter, llr_max, off, hard_out, return_infobits, t.slots,

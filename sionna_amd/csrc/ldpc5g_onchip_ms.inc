@@ -1,7 +1,7 @@
 // Body of the explicit-message engine (see ldpc5g_onchip_ms.hip): the kernel template and its launcher for ONE
 // check-node rule.  Included by ldpc5g_onchip_ms.hip (min-sum), ldpc5g_onchip_ms_phi.hip and ldpc5g_onchip_ms_tanh.hip -
 // one translation unit per rule, so that the three sets of 12 kernels compile in parallel.
-#include "ldpc5g.h"
+#include "ldpc5g_io.h"
 #include "bp_math.h"
 
 namespace samd {
@@ -355,10 +355,7 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_ms_kernel(
 
   for (int b = blockIdx.x; b < batch; b += gridDim.x) {
     const float* row = llr_in + (size_t)b * p.n;
-    // decoding.py:552-565: clip, then logits -> LLR; "+ 0.f" turns -0 into +0 (numerically the same LLR)
-    // so that no total and no v2c is ever -0 and the sign bit of a v2c equals (v2c < 0)
-    for (int v = tid; v < nx; v += NT)
-      llr[v] = (v < n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
+    for (int v = tid; v < nx; v += NT) llr[v] = channel_llr<true>(p, row, v, n_vn, llr_max);
     __syncthreads();
     for (int seg = 0; seg < 2; ++seg) {                              // v2c of iteration 0 = channel LLR, all columns
       const int t0 = seg ? f0 : v0, t1 = seg ? f1 : v1;
@@ -513,20 +510,9 @@ __global__ __launch_bounds__(NW * 64) void ldpc5g_decode_ms_kernel(
       __syncthreads();
       SAMD_TRACE_MARK(4)
     }
-    // ---------------- output (decoding.py:620-626, 1486-1531); llr[] now holds the marginals
-    if (return_infobits) {
-      float* o = out + (size_t)b * p.k;
-      for (int v = tid; v < p.k; v += NT) {
-        const float x = clampf(llr[v], -llr_max, llr_max);
-        o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    } else {
-      float* o = out + (size_t)b * p.n;
-      for (int i = tid; i < p.n; i += NT) {
-        const float x = clampf(llr[short_to_full(p, out_to_short(p, i))], -llr_max, llr_max);
-        o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    }
+    // llr[] now holds the marginals
+    store_codeword(p, out, (size_t)b, [&](int v) { return llr[v]; }, llr_max, hard_out,
+                   return_infobits, tid, NT);
     __syncthreads();
   }
 }
@@ -583,8 +569,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
 
   for (int b = blockIdx.x; b < batch; b += gridDim.x) {
     const float* row = llr_in + (size_t)b * p.n;
-    for (int v = tid; v < nx; v += NT)
-      llr[v] = (v < n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
+    for (int v = tid; v < nx; v += NT) llr[v] = channel_llr<true>(p, row, v, n_vn, llr_max);
     __syncthreads();
     for (int seg = 0; seg < 2; ++seg) {                              // v2c of iteration 0 = channel LLR, all columns
       const int t0 = seg ? f0 : v0, t1 = seg ? f1 : v1;
@@ -704,20 +689,9 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_msg_kernel(
       ms_phase_barrier(last || !lds_bar);
       SAMD_ITRACE(3000)
     }
-    // ---------------- output (decoding.py:620-626, 1486-1531); llr[] now holds the marginals
-    if (return_infobits) {
-      float* o = out + (size_t)b * p.k;
-      for (int v = tid; v < p.k; v += NT) {
-        const float x = clampf(llr[v], -llr_max, llr_max);
-        o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    } else {
-      float* o = out + (size_t)b * p.n;
-      for (int i = tid; i < p.n; i += NT) {
-        const float x = clampf(llr[short_to_full(p, out_to_short(p, i))], -llr_max, llr_max);
-        o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    }
+    // llr[] now holds the marginals
+    store_codeword(p, out, (size_t)b, [&](int v) { return llr[v]; }, llr_max, hard_out,
+                   return_infobits, tid, NT);
     __syncthreads();
   }
 }
@@ -740,11 +714,8 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
   }
   float* llr_ws = nullptr;
   if (h->bp.llr_global) {
-    if (!workspace || workspace_bytes < onchip_bp_workspace_bytes(h, batch)) {
-      set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
-      return SAMD_ERR_WORKSPACE;
-    }
-    llr_ws = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
+    const int rc = decode_workspace(workspace, workspace_bytes, onchip_bp_workspace_bytes(h, batch), &llr_ws);
+    if (rc != SAMD_OK) return rc;
   }
   const bool pow2 = (h->z & (h->z - 1)) == 0;
   if (h->ms.g_ok && h->bp.waves == 16) {
@@ -758,7 +729,6 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
     const int zm = h->z == 128 ? 2 : (pow2 ? 1 : 0);
     const gkern_t fn = gk[(h->bp.llr_global ? 3 : 0) + zm];
     SAMD_SET_MAX_LDS(fn, 160 * 1024);
-    const int nbu_g = (h->n_vn + h->z - 1) / h->z;
     const RateMatch rm_g = make_rate_match(h);
     const float off_g = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
     // boxplus-phi: 512 bytes behind the messages for the table of the defined logarithm when they fit (else global memory)
@@ -768,7 +738,7 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
       return SAMD_ERR_UNSUPPORTED;                             // the caller runs the first boxplus kernel (table from global memory)
     }
     hipLaunchKernelGGL(fn, dim3(onchip_bp_grid(h, batch)), dim3(1024), onchip_bp_lds_bytes(h) + (phi_lds_g ? 512 : 0), st,
-                       llr, out, llr_ws, rm_g, h->n_cn, nbu_g, batch, num_iter, llr_max, off_g, hard_out, return_infobits,
+                       llr, out, llr_ws, rm_g, h->n_cn, used_cols(h), batch, num_iter, llr_max, off_g, hard_out, return_infobits,
                        h->bp.edges * h->z, h->ms.col_ent.get(), h->ms.vn_ptr.get(),
                        reinterpret_cast<const int2*>(h->ms.vn_list.get()), h->ms.g_ptr.get(),
                        reinterpret_cast<const int2*>(h->ms.g_cn.get()), reinterpret_cast<const int2*>(h->ms.g_vn.get()),
@@ -790,18 +760,17 @@ static int launch_onchip_ms_mode(const samd_ldpc5g* h, const float* llr, float* 
   const int wi = h->bp.llr_global ? 5 : (nw == 16 ? 0 : nw == 8 ? 1 : nw == 4 ? 2 : nw == 2 ? 3 : 4);
   const int ki = 2 * wi + (pow2 ? 1 : 0);
   SAMD_SET_MAX_LDS(kerns[ki], 160 * 1024);
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
   const RateMatch rm = make_rate_match(h);
   const float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
   // (several workgroups may share a CU here: the table's 512 bytes count per workgroup)
-  const size_t per_cu_wg = std::min<size_t>((size_t)(kDecWaves / nw), std::max<size_t>(1, (160 * 1024) / onchip_bp_lds_bytes(h)));
+  const size_t per_cu_wg = onchip_wgs_per_cu(nw, onchip_bp_lds_bytes(h));
   const int phi_lds = MODE == SAMD_CN_BOXPLUS_PHI ? 1 : 0;
   if (phi_lds && (onchip_bp_lds_bytes(h) + 512) * per_cu_wg > 160 * 1024) {
     set_error("no room for the boxplus-phi table beside the messages");
     return SAMD_ERR_UNSUPPORTED;
   }
   hipLaunchKernelGGL(kerns[ki], dim3(onchip_bp_grid(h, batch)), dim3(nw * 64), onchip_bp_lds_bytes(h) + (phi_lds ? 512 : 0),
-                     st, llr, out, llr_ws, rm, h->n_cn, nbu, batch, num_iter, llr_max, off, hard_out, return_infobits,
+                     st, llr, out, llr_ws, rm, h->n_cn, used_cols(h), batch, num_iter, llr_max, off, hard_out, return_infobits,
                      h->bp.edges * h->z, h->ms.col_ent.get(), h->ms.cn_ptr.get(),
                      reinterpret_cast<const int2*>(h->ms.cn_list.get()),
                      h->ms.vn_ptr.get(), reinterpret_cast<const int2*>(h->ms.vn_list.get()),

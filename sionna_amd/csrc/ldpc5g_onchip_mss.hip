@@ -13,7 +13,7 @@
 // (27 VALU operations per edge); here a spilled edge costs 16 B of L2 traffic per iteration and 15 operations.
 // Used while at most ~27 % of the edges are spilled (codes with 160 KB < 4 E Z <~ 215 KB, e.g. k=6144 rate 2/3,
 // k=5632 rate 1/2): +9 ... +16 % over the compressed engine; larger codes stay on the compressed engine.
-#include "ldpc5g.h"
+#include "ldpc5g_io.h"
 #include "bp_math.h"
 
 namespace samd {
@@ -213,8 +213,7 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_mss_kernel(
 
   for (int b = blockIdx.x; b < batch; b += gridDim.x) {
     const float* row = llr_in + (size_t)b * p.n;
-    for (int v = tid; v < nx; v += NT)
-      llr[v] = (v < n_vn) ? (-1.f * clampf(recover_llr(p, row, v, llr_max), -llr_max, llr_max)) + 0.f : 0.f;
+    for (int v = tid; v < nx; v += NT) llr[v] = channel_llr<true>(p, row, v, n_vn, llr_max);
     __syncthreads();
     for (int seg = 0; seg < 2; ++seg) {                              // v2c of iteration 0 = channel LLR, all columns
       const int t0 = seg ? f0 : v0, t1 = seg ? f1 : v1;
@@ -315,19 +314,8 @@ __global__ __launch_bounds__(1024) void ldpc5g_decode_mss_kernel(
       }
       __syncthreads();
     }
-    if (return_infobits) {
-      float* o = out + (size_t)b * p.k;
-      for (int v = tid; v < p.k; v += NT) {
-        const float x = clampf(llr[v], -llr_max, llr_max);
-        o[v] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    } else {
-      float* o = out + (size_t)b * p.n;
-      for (int i = tid; i < p.n; i += NT) {
-        const float x = clampf(llr[short_to_full(p, out_to_short(p, i))], -llr_max, llr_max);
-        o[i] = hard_out ? ((0.f >= x) ? 1.f : 0.f) : -1.f * x;
-      }
-    }
+    store_codeword(p, out, (size_t)b, [&](int v) { return llr[v]; }, llr_max, hard_out,
+                   return_infobits, tid, NT);
     __syncthreads();
   }
 }
@@ -437,16 +425,12 @@ int build_onchip_mss_tables(samd_ldpc5g* h, const BaseRows& by_row) {
 }
 
 static int mss_grid(const samd_ldpc5g* h, int batch) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return std::min(batch, cus);
+  return std::min(batch, device_cus());
 }
 
 size_t onchip_mss_workspace_bytes(const samd_ldpc5g* h, int batch) {
   if (!h->sp.ok || batch <= 0) return 0;
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
-  return (size_t)mss_grid(h, batch) * ((size_t)nbu * h->z + h->sp.g_floats) * sizeof(float) + 256;
+  return (size_t)mss_grid(h, batch) * ((size_t)used_cols(h) * h->z + h->sp.g_floats) * sizeof(float) + 256;
 }
 
 int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int batch, int num_iter, int cn_mode,
@@ -456,11 +440,9 @@ int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int ba
     set_error("no spill schedule for this code");
     return SAMD_ERR_UNSUPPORTED;
   }
-  if (!workspace || workspace_bytes < onchip_mss_workspace_bytes(h, batch)) {
-    set_error("workspace too small (samd_ldpc5g_decode_workspace_bytes)");
-    return SAMD_ERR_WORKSPACE;
-  }
-  float* ws = reinterpret_cast<float*>(align_up((size_t)workspace, 256));
+  float* ws = nullptr;
+  const int rc = decode_workspace(workspace, workspace_bytes, onchip_mss_workspace_bytes(h, batch), &ws);
+  if (rc != SAMD_OK) return rc;
   const bool pow2 = (h->z & (h->z - 1)) == 0;
   typedef void (*kern_t)(const float*, float*, float*, RateMatch, int, int, int, int, float, float, int, int, int,
                          const int32_t*, const int32_t*, const int2*, const int32_t*, const int2*);
@@ -471,10 +453,9 @@ int launch_onchip_mss(const samd_ldpc5g* h, const float* llr, float* out, int ba
   const int mi = cn_mode == SAMD_CN_BOXPLUS_PHI ? 1 : cn_mode == SAMD_CN_BOXPLUS ? 2 : cn_mode == SAMD_CN_BOXPLUS_PHI_FAST ? 3 : 0;
   const kern_t fn = kerns[2 * mi + (pow2 ? 1 : 0)];
   SAMD_SET_MAX_LDS(fn, 160 * 1024);
-  const int nbu = (h->n_vn + h->z - 1) / h->z;
   const RateMatch rm = make_rate_match(h);
   const float off = (cn_mode == SAMD_CN_OFFSET_MINSUM) ? offset : 0.f;
-  hipLaunchKernelGGL(fn, dim3(mss_grid(h, batch)), dim3(1024), h->sp.lds_bytes, st, llr, out, ws, rm, h->n_cn, nbu, batch,
+  hipLaunchKernelGGL(fn, dim3(mss_grid(h, batch)), dim3(1024), h->sp.lds_bytes, st, llr, out, ws, rm, h->n_cn, used_cols(h), batch,
                      num_iter, llr_max, off, hard_out, return_infobits, h->sp.g_floats, h->sp.col_ent.get(),
                      h->sp.cn_ptr.get(), reinterpret_cast<const int2*>(h->sp.cn_list.get()), h->sp.vn_ptr.get(),
                      reinterpret_cast<const int2*>(h->sp.vn_list.get()));

@@ -441,13 +441,10 @@ static size_t scl_lds_bytes(int n, int L, int num_ops, size_t real = sizeof(floa
 // resident workgroups (= codewords in flight): as many as the list state of the engine that runs lets a CU hold
 static int scl_grid(int batch, int n, int L, bool reg_engine) {
   const size_t lds = reg_engine ? scl_reg_lds_bytes(n, L) : scl_lds_bytes(n, L, 0);
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   static CachedOpt per_cu_opt("SAMD_SCL_PER_CU");
   const size_t cap = (size_t)std::max<long>(1, per_cu_opt.get(32));   // one wave per workgroup: 8 per SIMD
   const size_t per_cu = std::min<size_t>(cap, std::max<size_t>(1, (160 * 1024) / lds));
-  return (int)std::min<size_t>((size_t)batch, (size_t)cus * per_cu);
+  return (int)std::min<size_t>((size_t)batch, (size_t)device_cus() * per_cu);
 }
 
 }  // namespace samd
