@@ -60,8 +60,13 @@ __device__ __forceinline__ void square_qam_llr(const float2 ys, const float no_v
     } else {
       // app: every level's exponential is evaluated ONCE, relative to the axis maximum M, and shared by the NB bit
       // positions: logsumexp over a set = M + log(sum of its shares), and M cancels in the difference of the two
-      // sets.  A set whose best member lies more than 80 below M would lose its terms to underflow - that bit
-      // position (rare below ~25 dB of SNR) takes the per-set maxima instead.
+      // sets.  demap_exp returns 0 for an exponential below 2^-126 (no denormal scaling), i.e. for a member more
+      // than 126 ln 2 = 87.34 below M: a set whose best member lies more than 64 below M (rare below
+      // ~25 dB of SNR) has its two sums recomputed against the sets' own maxima instead.  Up to the switch a set's
+      // sum is >= e^-64 = 2^-92.4 while its 2^(NB-1) <= 16 members lose less than 2^-126 each, 2^-122 together:
+      // less than 2^-29.6 = u / 50 of the sum (u = 2^-24).  Any switch up to ln(2^-25 / 2^-122) = 67.2 keeps the
+      // loss below u / 2 (the former 80 lost up to e^-(87.34 - 80) = 6.5e-4 of a sum); 64 leaves room for the
+      // rounding of the compared difference.
       const float mall = fmaxf(mx0[NB - 1], mx1[NB - 1]);
       float ex[L];
 #pragma unroll
@@ -71,9 +76,9 @@ __device__ __forceinline__ void square_qam_llr(const float2 ys, const float no_v
 #pragma unroll
       for (int t = 0; t < NB; ++t) {
         const int p = NB - 1 - t;
-        // sums in [e^-80, 2^(NB-1)]: normal numbers; ln 2 (log2 s1 - log2 s0)
+        // sums in [e^-64, 2^(NB-1)]: normal numbers; ln 2 (log2 s1 - log2 s0)
         float r = (__builtin_amdgcn_logf(s1[p]) - __builtin_amdgcn_logf(s0[p])) * 0.693147180559945f;
-        if (mall - fminf(mx0[p], mx1[p]) > 80.f) {
+        if (mall - fminf(mx0[p], mx1[p]) > 64.f) {
           float a0 = 0.f, a1 = 0.f;
 #pragma unroll
           for (int j = 0; j < L; ++j) {

@@ -118,7 +118,9 @@ __global__ __launch_bounds__(256) void demap_kernel(const float2* __restrict__ y
 #pragma unroll
         for (int i = 0; i < M; ++i) {
           const int bit = (c >> (M - 1 - i)) & 1;
-          if (bit) sm[i][1] += exp_core_f32(e - mx[i][1]); else sm[i][0] += exp_core_f32(e - mx[i][0]);
+          // (clamped: exp_core_f32 is for moderate arguments - below -2^31 / log2(e) = -1.5e9 its residual of the product exceeds
+          // 128 and the exponential came back as inf, e.g. at no = 0.  e^-104 < 2^-150 adds nothing to a sum >= 1 either)
+          if (bit) sm[i][1] += exp_core_f32(fmaxf(e - mx[i][1], -104.f)); else sm[i][0] += exp_core_f32(fmaxf(e - mx[i][0], -104.f));
         }
       }
 #pragma unroll

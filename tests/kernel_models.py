@@ -743,3 +743,156 @@ def cdl_cir_model(tables, seed, call, batch, num_time_steps, sampling_frequency,
             ay[t][:, pos] += gr * sn + gi * cs
     out = (ax + 1j * ay).astype(np.complex64)                                      # [T, B, No, U, S]
     return np.ascontiguousarray(np.transpose(out, [1, 3, 4, 2, 0]))[:, None, :, None]
+
+
+# ------------------------------------------------------------------ LLR demappers (csrc/demap_core.h, csrc/mapping.hip)
+_LOG2E_HI, _LOG2E_LO = np.uint32(0x3fb8aa3b).view(F), np.uint32(0x32a5705f).view(F)
+_LN2_HI, _LN2_LO = np.uint32(0x3f317217).view(F), np.uint32(0x3377d1cf).view(F)
+_TINY = np.finfo(F).tiny
+
+
+def _fma(a, b, c):
+    """float32 fma: the product of two float32 is exact in float64; the sum rounds once more at 2^-53, far below float32"""
+    return (a.astype(np.float64) * np.float64(b) + c.astype(np.float64)).astype(F)
+
+
+def _hw_exp2(t):
+    """v_exp_f32 stand-in: NumPy's float32 exp2; results below 2^-126 are returned as 0 (no denormal scaling)"""
+    with np.errstate(under="ignore"):
+        r = np.exp2(t.astype(F)).astype(F)
+    return np.where(r < _TINY, F(0), r)
+
+
+def _demap_exp(x, plain=False):
+    x = x.astype(F)
+    t = x * _LOG2E_HI
+    if plain:
+        return _hw_exp2(t)
+    lo = _fma(x, _LOG2E_LO, _fma(x, _LOG2E_HI, -t))
+    return _hw_exp2(t + lo)
+
+
+def _exp_core(x):
+    x = x.astype(F)
+    t = x * _LOG2E_HI
+    lo = _fma(x, _LOG2E_LO, _fma(x, _LOG2E_HI, -t))
+    r = np.rint(t)
+    f = (t - r) + lo
+    with np.errstate(under="ignore"):
+        return np.ldexp(np.exp2(f).astype(F), np.clip(r, -100000, 100000).astype(np.int32)).astype(F)
+
+
+def _log_core(x):
+    with np.errstate(divide="ignore"):
+        y = np.log2(x.astype(F)).astype(F)
+    r = y * _LN2_HI
+    return r + _fma(y, _LN2_LO, _fma(y, _LN2_HI, -r))
+
+
+def _bit_reduce(e, op):
+    """bit_reduce<L> of demap_core.h on e [n, L]: r0 / r1 [n, NB], position p = label bit p (LSB = 0), the same tree"""
+    L = e.shape[1]
+    if L == 2:
+        return e[:, :1].copy(), e[:, 1:2].copy()
+    ev, od = e[:, 0], e[:, 1]
+    for k in range(1, L // 2):
+        ev, od = op(ev, e[:, 2 * k]), op(od, e[:, 2 * k + 1])
+    r0, r1 = _bit_reduce(op(e[:, 0::2], e[:, 1::2]), op)
+    return np.concatenate([ev[:, None], r0], axis=1), np.concatenate([od[:, None], r1], axis=1)
+
+
+def _model_no(no, n, fault):
+    no = np.asarray(no, F).reshape(-1)
+    if no.size > 1 and fault == "neighbour_no":
+        no = np.roll(no, -1)                     # the prefetched value of the next symbol
+    if no.size > 1 and fault == "no0":
+        no = no[:1]
+    return np.broadcast_to(no, (n,))
+
+
+def demap_square_model(y, no, levels, method, hard_out=False, threshold=64.0, fault=None):
+    """``demap_square_qam_kernel`` / ``square_qam_llr``, operation by operation in float32: one reciprocal per symbol, the
+    ``bit_reduce`` tree for maxima and sums, ``demap_exp`` with its extended-precision product and the flush of exponentials below
+    2^-126, the switch to per-set maxima above ``threshold``.  y [n] complex64, no [1] or [n], levels [2^NB] -> [n, 2 NB]"""
+    y = np.asarray(y, np.complex64).reshape(-1)
+    lev = np.asarray(levels, F).copy()
+    if fault == "level_4ulp":
+        for _ in range(4):
+            lev[0] = np.nextafter(lev[0], F(np.inf))
+    n, L = y.size, len(lev)
+    nb = int(np.log2(L))
+    nv = _model_no(no, n, fault)
+    ln2 = F(0.693147180559945)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        inv = F(1) / (nv if fault == "no_tiny" else np.maximum(nv, _TINY))
+        llr = np.zeros((n, 2 * nb), F)
+        for ax in range(2):
+            ya = (y.imag if (ax == 0) == (fault == "axes_swapped") else y.real).astype(F)
+            d = ya[:, None] - lev[None, :]
+            e = -(d * d) * inv[:, None]
+            mx0, mx1 = _bit_reduce(e, np.maximum)
+            mall = np.maximum(mx0[:, nb - 1], mx1[:, nb - 1])
+            if method == "app":
+                ex = _demap_exp(e - mall[:, None], plain=fault == "plain_product")
+                s0, s1 = _bit_reduce(ex, np.add)
+            for t in range(nb):
+                p = t if fault == "bit_order" else nb - 1 - t
+                if method != "app":
+                    llr[:, 2 * t + ax] = mx1[:, p] - mx0[:, p]
+                    continue
+                r = (np.log2(s1[:, p]) - np.log2(s0[:, p])).astype(F) * ln2
+                if fault != "no_threshold":
+                    a0, a1 = np.zeros(n, F), np.zeros(n, F)
+                    for j in range(L):
+                        if (j >> p) & 1:
+                            a1 = a1 + _demap_exp(e[:, j] - mx1[:, p], plain=fault == "plain_product")
+                        else:
+                            a0 = a0 + _demap_exp(e[:, j] - mx0[:, p], plain=fault == "plain_product")
+                    rb = (np.log2(a1).astype(F) * ln2 + mx1[:, p]) - (np.log2(a0).astype(F) * ln2 + mx0[:, p])
+                    r = np.where(mall - np.minimum(mx0[:, p], mx1[:, p]) > F(threshold), rb, r)
+                llr[:, 2 * t + ax] = r
+    return (llr > 0).astype(F) if hard_out else llr
+
+
+def demap_generic_model(y, no, points, method, prior=None, hard_out=False, fault=None):
+    """``demap_kernel<M, MAXLOG>``: the IEEE division, pass 1 (per (bit, value) maxima), pass 2 (ascending-c sums of ``exp_core_f32``
+    against the set's own maximum), ``log_core_f32``, the a-priori terms log_sigmoid(+-prior_i) summed over i from 0.
+    y [n] complex64, no [1] or [n], points [2^m] complex64, prior None, [m] or [n, m] -> [n, m]"""
+    y = np.asarray(y, np.complex64).reshape(-1)
+    pts = np.asarray(points, np.complex64)
+    n, P = y.size, len(pts)
+    m = int(np.log2(P))
+    nv = _model_no(no, n, fault)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        n0 = nv if fault == "no_tiny" else np.maximum(nv, _TINY)
+        if prior is not None:
+            p = np.broadcast_to(np.asarray(prior, F).reshape(-1, m), (n, m))
+            p = -p if fault == "prior_sign" else p
+            z_p, z_n = np.log1p(np.exp(p)).astype(F), np.log1p(np.exp(-p)).astype(F)
+            ls1 = np.where(p < 0, p - z_p, -z_n).astype(F)
+            ls0 = np.where(-p < 0, -p - z_n, -z_p).astype(F)
+
+        def expo(c):
+            dr, di = y.real.astype(F) - pts[c].real, y.imag.astype(F) - pts[c].imag
+            e = -(dr * dr + di * di) / n0
+            if prior is not None:
+                ps = np.zeros(n, F)
+                for i in range(m):
+                    ps = ps + (ls1[:, i] if (c >> (m - 1 - i)) & 1 else ls0[:, i])
+                e = ps + e
+            return e.astype(F)
+
+        ex = np.stack([expo(c) for c in range(P)], axis=1)                       # both passes recompute the same values
+        bits = (np.arange(P)[:, None] >> np.arange(m - 1, -1, -1)) & 1          # [P, m]
+        mx = np.stack([[np.max(ex[:, bits[:, i] == b], axis=1) for b in (0, 1)] for i in range(m)])        # [m, 2, n]
+        if method != "app":
+            llr = (mx[:, 1] - mx[:, 0]).T
+        else:
+            sm = np.zeros((m, 2, n), F)
+            for c in range(P):
+                for i in range(m):
+                    b = bits[c, i]
+                    sm[i, b] = sm[i, b] + _exp_core(ex[:, c] - mx[i, b] if fault == "no_clamp" else np.maximum(ex[:, c] - mx[i, b], F(-104)))
+            llr = ((_log_core(sm[:, 1]) + mx[:, 1]) - (_log_core(sm[:, 0]) + mx[:, 0])).T
+    llr = np.ascontiguousarray(llr, F)
+    return (llr > 0).astype(F) if hard_out else llr
