@@ -5,8 +5,8 @@
 //   SymbolLogits2Moments.call mapping.py:1125-1138
 //   PAM2QAM.__call__ (logits) mapping.py:1304-1314
 // The same argument layouts as the float32 entries of csrc/mapping.hip; one lane per row, libm exp / log in double, sums in
-// ascending point order.  Held to oracle/mapping.py (float64) at 1e-9 (tests/test_gpu_double.py); the tuned kernels are the
-// float32 ones.
+// ascending point order.  Held to oracle/mapping.py (float64) at 1e-9 (tests/test_gpu_double.py) and, on every output, to 2^-29 times
+// the float32 kernels' derived bound (tests/test_gpu_symbol_edges.py); the tuned kernels are the float32 ones.
 #include "common.h"
 
 namespace samd {
@@ -75,7 +75,8 @@ __global__ __launch_bounds__(256) void logits2llrs64_kernel(const double* __rest
         llr = mx[1] - mx[0];
       } else {
         for (int c = 0; c < P; ++c) { const int b = (c >> (M - 1 - i)) & 1; sm[b] += exp(expo(c) - mx[b]); }
-        llr = (log(sm[1]) + mx[1]) - (log(sm[0]) + mx[0]);
+        // (a set whose maximum is not finite - every member at -inf - reduces to that maximum, like tf.reduce_logsumexp)
+        llr = (isfinite(mx[1]) ? log(sm[1]) + mx[1] : mx[1]) - (isfinite(mx[0]) ? log(sm[0]) + mx[0] : mx[0]);
       }
       out[s * M + i] = hard_out ? (llr > 0.0 ? 1.0 : 0.0) : llr;
     }

@@ -351,11 +351,19 @@ __global__ __launch_bounds__(256) void logits2llrs_kernel(const float* __restric
         const float e = expo(c);
 #pragma unroll
         for (int i = 0; i < M; ++i) {
-          if ((c >> (M - 1 - i)) & 1) sm[i][1] += exp_core_f32(e - mx[i][1]); else sm[i][0] += exp_core_f32(e - mx[i][0]);
+          // (clamped as in demap_kernel: exp_core_f32 is for moderate arguments - a member at -inf gave NaN, one more than 1.5e9
+          // below the set's maximum inf; e^-104 < 2^-150 adds nothing to a sum >= 1)
+          if ((c >> (M - 1 - i)) & 1) sm[i][1] += exp_core_f32(fmaxf(e - mx[i][1], -104.f)); else sm[i][0] += exp_core_f32(fmaxf(e - mx[i][0], -104.f));
         }
       }
+      // a set whose maximum is not finite reduces to that maximum: all members at -inf (the logits LLRs2SymbolLogits forms for an
+      // LLR of +-inf) give -inf and an LLR of -+inf, as tf.reduce_logsumexp does (-inf - -inf is NaN, not a sum)
 #pragma unroll
-      for (int i = 0; i < M; ++i) llr[i] = (log_core_f32(sm[i][1]) + mx[i][1]) - (log_core_f32(sm[i][0]) + mx[i][0]);
+      for (int i = 0; i < M; ++i) {
+        const float r1 = isfinite(mx[i][1]) ? log_core_f32(sm[i][1]) + mx[i][1] : mx[i][1];
+        const float r0 = isfinite(mx[i][0]) ? log_core_f32(sm[i][0]) + mx[i][0] : mx[i][0];
+        llr[i] = r1 - r0;
+      }
     }
     float* o = out + s * M;
 #pragma unroll

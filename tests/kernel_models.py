@@ -896,3 +896,144 @@ def demap_generic_model(y, no, points, method, prior=None, hard_out=False, fault
             llr = ((_log_core(sm[:, 1]) + mx[:, 1]) - (_log_core(sm[:, 0]) + mx[:, 0])).T
     llr = np.ascontiguousarray(llr, F)
     return (llr > 0).astype(F) if hard_out else llr
+
+
+# ------------------------------------------------------------------ symbol-domain mapping kernels (csrc/mapping.hip)
+def _f32_log_sigmoid(p, naive=False):
+    p = np.asarray(p, F)
+    with np.errstate(all="ignore"):
+        if naive:
+            return np.log(F(1) / (F(1) + np.exp(-p).astype(F))).astype(F)
+        return np.where(p < 0, p - np.log1p(np.exp(p).astype(F)).astype(F), -np.log1p(np.exp(-p).astype(F)).astype(F)).astype(F)
+
+
+def _first_argmax_strict(e, last=False):
+    """``if (e > mx) { mx = e; arg = c; }`` from -inf, arg = 0 (``last``: >=, the seeded fault)"""
+    n, P = e.shape
+    mx, arg = np.full(n, -np.inf, F), np.zeros(n, np.int32)
+    for c in range(P):
+        up = (e[:, c] >= mx) if last else (e[:, c] > mx)
+        mx, arg = np.where(up, e[:, c], mx), np.where(up, c, arg).astype(np.int32)
+    return mx, arg
+
+
+def symbol_demap_model(y, no, points, prior=None, hard_out=False, fault=None):
+    """``symbol_demap_kernel``: e_c = -(sqrtf(dr^2 + di^2))^2 / no (+ prior_c), strict first maximum, ascending sum of expf(e_c - mx),
+    mx + logf(sum), e_c - lse.  y [n] complex64, no [1] or [n], points [P] complex64, prior None / [P] / [n, P] -> [n, P] (int32 [n])"""
+    y = np.asarray(y, np.complex64).reshape(-1)
+    pts = np.asarray(points, np.complex64)
+    n, P = y.size, len(pts)
+    nv = np.broadcast_to(np.asarray(no, F).reshape(-1), (n,))[:, None]
+    with np.errstate(all="ignore"):
+        dr, di = y.real.astype(F)[:, None] - pts.real[None, :], y.imag.astype(F)[:, None] - pts.imag[None, :]
+        d = np.sqrt(dr * dr + di * di).astype(F)
+        e = (-(d * d) / nv).astype(F)
+        if prior is not None:
+            e = (e + np.broadcast_to(np.asarray(prior, F).reshape(-1, P), (n, P))).astype(F)
+        mx, arg = _first_argmax_strict(e, last=fault == "last_max")
+        if hard_out:
+            return arg
+        sh = np.zeros(n, F) if fault == "no_shift" else mx
+        s = np.zeros(n, F)
+        for c in range(P - 1 if fault == "sum_pm1" else P):
+            s = s + np.exp(e[:, c] - sh).astype(F)
+        lse = sh + np.log(s).astype(F)
+        return (e - lse[:, None]).astype(F)
+
+
+def logits2llrs_model(z, m, method, prior=None, hard_out=False, fault=None):
+    """``logits2llrs_kernel<M, MAXLOG>``: exponents = logits (+ sum_i log_sigmoid(+-prior_i) from 0), per (bit, value) maxima, ascending
+    sums of ``exp_core_f32`` of the argument clamped at -104, ``log_core_f32`` + maximum - or the maximum itself where it is not finite
+    (a whole set at -inf reduces to -inf, tf.reduce_logsumexp).  fault "unfixed": the kernel before the clamp and the empty-set rule"""
+    z = np.asarray(z, F).reshape(-1, 1 << m)
+    n, P = z.shape
+    bits = (np.arange(P)[:, None] >> (np.arange(m) if fault == "lsb_first" else np.arange(m - 1, -1, -1))) & 1
+    with np.errstate(all="ignore"):
+        ex = z
+        if prior is not None:
+            p = np.asarray(prior, F).reshape(-1, m)
+            p = np.broadcast_to(p[:1] if fault == "prior_as_vec" else p, (n, m))
+            ls = np.stack([_f32_log_sigmoid(-p), _f32_log_sigmoid(p)], axis=-1)
+            ex = np.zeros((n, P), F)
+            for c in range(P):
+                ps = np.zeros(n, F)
+                for i in range(m):
+                    ps = ps + ls[:, i, (c >> (m - 1 - i)) & 1]
+                ex[:, c] = ps + z[:, c]
+        mx = np.stack([[np.max(ex[:, bits[:, i] == b], axis=1) for b in (0, 1)] for i in range(m)])        # [m, 2, n]
+        if method != "app":
+            llr = (mx[:, 1] - mx[:, 0]).T
+        else:
+            sm = np.zeros((m, 2, n), F)
+            for c in range(P):
+                for i in range(m):
+                    b = bits[c, i]
+                    x = ex[:, c] - mx[i, b]
+                    sm[i, b] = sm[i, b] + _exp_core(x if fault in ("unfixed", "unclamped") else np.maximum(x, F(-104)))
+            r = _log_core(sm) + mx
+            if fault not in ("unfixed", "no_empty_rule"):
+                r = np.where(np.isfinite(mx), r, mx)
+            llr = (r[:, 1] - r[:, 0]).T
+    llr = np.ascontiguousarray(llr, F)
+    return (llr > 0).astype(F) if hard_out else llr
+
+
+def llrs2logits_model(llrs, m, hard_out=False, fault=None):
+    """``llrs2logits_kernel``: the 2 m log-sigmoids of a row, then per point the sum over j from 0; hard_out: strict first maximum"""
+    l = np.asarray(llrs, F).reshape(-1, m)
+    n, P = l.shape[0], 1 << m
+    ls = np.stack([_f32_log_sigmoid(-l, fault == "naive_log_sigmoid"), _f32_log_sigmoid(l, fault == "naive_log_sigmoid")], axis=-1)
+    if fault == "sign_swapped":
+        ls[:, 0] = ls[:, 0, ::-1]
+    out = np.zeros((n, P), F)
+    with np.errstate(all="ignore"):
+        for c in range(P):
+            acc = np.zeros(n, F)
+            for j in range(m):
+                acc = acc + ls[:, j, (c >> (m - 1 - j)) & 1]
+            out[:, c] = acc
+    return _first_argmax_strict(out, last=fault == "last_max")[1] if hard_out else out
+
+
+def logits2moments_model(z, points, fault=None):
+    """``logits2moments_kernel``: maximum, den = ascending sum of expf(z_c - mx), the weights expf(z_c - mx) / den formed again for the
+    mean and again for the variance about the COMPUTED mean.  -> (mean complex64 [n], var float32 [n])"""
+    pts = np.asarray(points, np.complex64)
+    P = len(pts)
+    z = np.asarray(z, F).reshape(-1, P)
+    n = z.shape[0]
+    xr, xi = pts.real.astype(F), pts.imag.astype(F)
+    with np.errstate(all="ignore"):
+        mx = z.max(-1) if n else np.zeros(0, F)
+        den = np.zeros(n, F)
+        for c in range(P):
+            den = den + np.exp(z[:, c] - (F(0) if fault == "den_unshifted" else mx)).astype(F)
+        mr, mi = np.zeros(n, F), np.zeros(n, F)
+        for c in range(P - 1 if fault == "sum_pm1" else P):
+            pc = np.exp(z[:, c] - mx).astype(F) / den
+            mr, mi = mr + pc * xr[c], mi + pc * xi[c]
+        v = np.zeros(n, F)
+        for c in range(P):
+            pc = np.exp(z[:, c] - mx).astype(F) / den
+            if fault == "var_cancel":
+                v = v + pc * (xr[c] * xr[c] + xi[c] * xi[c])
+                continue
+            dr, di = (xr[c] - mr, xi[c] - mi) if fault != "var_about_0" else (np.broadcast_to(xr[c], (n,)), np.broadcast_to(xi[c], (n,)))
+            v = v + pc * (dr * dr + di * di)
+        if fault == "var_cancel":
+            v = v - (mr * mr + mi * mi)
+    return (mr + 1j * mi).astype(np.complex64), v.astype(F)
+
+
+def pam2qam_model(pam1, pam2, nbh, fault=None):
+    """``pam2qam_logits_kernel``: out[i P + j] = pam1[t >> nbh] + pam2[t & (P - 1)], t = the interleaved label of (i, j)"""
+    P = 1 << nbh
+    a, b = np.asarray(pam1, F).reshape(-1, P), np.asarray(pam2, F).reshape(-1, P)
+    out = np.zeros((a.shape[0], P * P), F)
+    for i in range(P):
+        for j in range(P):
+            t = 0
+            for k in range(nbh):
+                t |= (((i >> (nbh - 1 - k)) & 1) << (2 * nbh - 1 - 2 * k)) | (((j >> (nbh - 1 - k)) & 1) << (2 * nbh - 2 - 2 * k))
+            out[:, i * P + j] = a[:, i] + b[:, j] if fault == "scatter" else a[:, t >> nbh] + b[:, t & (P - 1)]
+    return out

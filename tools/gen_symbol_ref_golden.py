@@ -11,6 +11,10 @@ TensorFlow (tools/ref_exec) for everything that works on SYMBOL logits / indices
                          [batch, num_tx, num_streams, num_data_symbols(, num_points)] :289-317, 531-560) on the "c4" link of
                          tests/golden/ofdm_rx_ref_golden.npz (inputs are read from that fixture)
 
+``gen_symbol_ref_golden.py edges`` writes tests/golden/symbol_edges_ref_golden.npz instead: the five mapping.py blocks of
+tests/symbol_f32.py at the inputs whose value must not be assumed - members and whole sets at -inf, LLRs of +-inf, no = 0, exact ties
+of the hard outputs - in float32 and float64.
+
 Run here (needs /root/reference); the fixture travels."""
 import os
 import sys
@@ -20,6 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "tests", "golden", "symbol_ref_golden.npz")
+OUT_EDGES = os.path.join(ROOT, "tests", "golden", "symbol_edges_ref_golden.npz")
 MIMO = [(4, 2, 2), (4, 2, 4), (8, 4, 4), (4, 4, 6), (2, 2, 6)]      # (rx antennas, streams, bits per symbol)
 
 
@@ -112,5 +117,53 @@ def main():
     print("wrote", OUT, os.path.getsize(OUT), "bytes")
 
 
+def edges():
+    """what the reference's own code returns where logits, LLRs or priors are infinite, no is 0, or the maximum is tied"""
+    from tools.gen_ofdm_rx_ref_golden import load
+    mp = load()[0]
+    inf = np.inf
+    out = {}
+    for prec, rt, ct in (("single", np.float32, np.complex64), ("double", np.float64, np.complex128)):
+        p = "f32" if prec == "single" else "f64"
+        with np.errstate(all="ignore"):
+            # SymbolLogits2LLRs, m = 2: members at -inf and -FLT_MAX, one whole set at -inf, every logit at -inf, all equal
+            z = np.array([[0., -inf, 1., 2.], [-inf, -inf, 1., 2.], [-inf, 3., -inf, 1.], [1., -inf, -inf, -inf], [-inf] * 4,
+                          [0.5] * 4, [0., -3.4028235e38, 1., -1e10], [2., 2., -inf, -inf]], rt)
+            pr = np.array([[1., -2.]] * 4 + [[inf, 1.], [-inf, inf], [0., 0.], [50., -50.]], rt)
+            out[f"l2l_z_{p}"], out[f"l2l_prior_{p}"] = z, pr
+            for meth in ("app", "maxlog"):
+                out[f"l2l_{meth}_{p}"] = np.asarray(mp.SymbolLogits2LLRs(meth, 2, precision=prec)(z))
+                out[f"l2l_{meth}_prior_{p}"] = np.asarray(mp.SymbolLogits2LLRs(meth, 2, precision=prec)(z, pr))
+                out[f"l2l_{meth}_hard_{p}"] = np.asarray(mp.SymbolLogits2LLRs(meth, 2, hard_out=True, precision=prec)(z)).astype(rt)
+            # LLRs2SymbolLogits, m = 3: +-inf, 0 (every point tied), +-104, +-1e4
+            l = np.array([[inf, 1., -1.], [-inf, inf, 0.], [0., 0., 0.], [104., -104., 88.], [1e4, -1e4, 20.], [-inf, -inf, -inf],
+                          [0., 5., 0.]], rt)
+            out[f"l2s_llrs_{p}"] = l
+            out[f"l2s_logits_{p}"] = np.asarray(mp.LLRs2SymbolLogits(3, precision=prec)(l))
+            out[f"l2s_hard_{p}"] = np.asarray(mp.LLRs2SymbolLogits(3, hard_out=True, precision=prec)(l)).astype(np.int32)
+            out[f"l2s_round_{p}"] = np.asarray(mp.SymbolLogits2LLRs("app", 3, precision=prec)(out[f"l2s_logits_{p}"]))
+            # SymbolDemapper, 16-QAM: y on a point, at 0 (four points tied) and off the points; no = 0, tiny and 1; a prior with -inf
+            pts = np.asarray(mp.Constellation("qam", 4, precision=prec).points)
+            y = np.array([pts[5], 0., 0.1 + 0.2j, pts[0] * 0.5 + pts[1] * 0.5], ct)
+            prior = np.zeros((4, 16), rt)
+            prior[:, 3] = -inf
+            prior[1, :8] = -inf
+            out[f"sd_y_{p}"], out[f"sd_prior_{p}"] = y, prior
+            for name, no in (("zero", 0.), ("tiny", float(np.finfo(np.float32).tiny)), ("one", 1.)):
+                blk = mp.SymbolDemapper("qam", 4, precision=prec)
+                out[f"sd_{name}_{p}"] = np.asarray(blk(y, rt(no)))
+                out[f"sd_{name}_hard_{p}"] = np.asarray(mp.SymbolDemapper("qam", 4, hard_out=True, precision=prec)(y, rt(no))).astype(np.int32)
+            out[f"sd_one_prior_{p}"] = np.asarray(mp.SymbolDemapper("qam", 4, precision=prec)(y, rt(1.), prior))
+            out[f"sd_one_prior_hard_{p}"] = np.asarray(mp.SymbolDemapper("qam", 4, hard_out=True, precision=prec)(y, rt(1.), prior)).astype(np.int32)
+            # SymbolLogits2Moments, 4-QAM: members at -inf, one finite member, uniform, a common offset
+            zm = np.array([[0., -inf, 1., -inf], [-inf, -inf, 2., -inf], [1e6] * 4, [0., 0., -inf, -inf], [-1e4, 0., -1e4, -1e4]], rt)
+            mean, var = mp.SymbolLogits2Moments("qam", 2, precision=prec)(zm)
+            out[f"mom_z_{p}"], out[f"mom_mean_{p}"], out[f"mom_var_{p}"] = zm, np.asarray(mean), np.asarray(var)
+    np.savez_compressed(OUT_EDGES, **out)
+    for k, v in out.items():
+        print(k, v.shape, v.dtype, np.array2string(np.asarray(v).reshape(-1)[:8], precision=4))
+    print("wrote", OUT_EDGES, os.path.getsize(OUT_EDGES), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    edges() if sys.argv[1:] == ["edges"] else main()

@@ -5,6 +5,8 @@
 //   log2  __builtin_amdgcn_logf(x),   x in [2^-116, 2^10]:   |f - log2 x| / max(|log2 x|, 1)
 //   expf  (device libm),              x in [-87, 0]:         |f - e^x| / e^x         (log_sigmoid of the prior path)
 //   log1pf (device libm),             x in [2^-126, 1]:      |f - log1p x| / log1p x
+//   logf  (device libm),              x in [1, 2^10]:        |f - ln x| / ln x       (the sum of SymbolDemapper's log-softmax,
+//                                                                                     tests/symbol_f32.py; ln 1 = 0 must be exact)
 //   demap_exp / exp_core_f32,         x in [-87, 0]:         |f - e^x| / e^x         (cross-checks of the derivation, not inputs)
 //   log_core_f32,                     x in [2^-116, 2^10]:   |f - ln x| / max(|ln x|, 1)
 // hipcc --offload-arch=gfx950 -O3 -ffp-contract=off exp_log_accuracy.hip -o exp_log_accuracy
@@ -15,7 +17,7 @@
 #include "../../sionna_amd/csrc/demap_core.h"
 using namespace samd;
 
-enum { F_EXP2, F_LOG2, F_EXPF, F_LOG1PF, F_DEMAP_EXP, F_EXP_CORE, F_LOG_CORE, F_COUNT };
+enum { F_EXP2, F_LOG2, F_EXPF, F_LOG1PF, F_LOGF, F_DEMAP_EXP, F_EXP_CORE, F_LOG_CORE, F_COUNT };
 
 template <int F>
 __global__ void sweep(unsigned lo, unsigned hi, unsigned sign, unsigned long long* worst, unsigned* where) {
@@ -30,6 +32,7 @@ __global__ void sweep(unsigned lo, unsigned hi, unsigned sign, unsigned long lon
     if constexpr (F == F_LOG2) { f = __builtin_amdgcn_logf(x); r = log2(xd); s = fmax(fabs(r), 1.); }
     if constexpr (F == F_EXPF) { f = expf(x); r = exp(xd); s = r; }
     if constexpr (F == F_LOG1PF) { f = log1pf(x); r = log1p(xd); s = r; }
+    if constexpr (F == F_LOGF) { f = logf(x); r = log(xd); s = r > 0. ? r : (f == 0. ? 1. : 0.); }
     if constexpr (F == F_DEMAP_EXP) { f = demap_exp(x); r = exp(xd); s = r; }
     if constexpr (F == F_EXP_CORE) { f = exp_core_f32(x); r = exp(xd); s = r; }
     if constexpr (F == F_LOG_CORE) { f = log_core_f32(x); r = log(xd); s = fmax(fabs(r), 1.); }
@@ -69,6 +72,7 @@ int main(int argc, char** argv) {
   rc |= run<F_LOG2>("log2", 1.2037062e-35f, 1024.f, dw, dat, out);           // 2^-116 ... 2^10
   rc |= run<F_EXPF>("expf", -1.17549435e-38f, -87.f, dw, dat, out);
   rc |= run<F_LOG1PF>("log1pf", 1.17549435e-38f, 1.f, dw, dat, out);
+  rc |= run<F_LOGF>("logf", 1.f, 1024.f, dw, dat, out);
   rc |= run<F_DEMAP_EXP>("demap_exp", -1.17549435e-38f, -87.f, dw, dat, out);
   rc |= run<F_EXP_CORE>("exp_core", -1.17549435e-38f, -87.f, dw, dat, out);
   rc |= run<F_LOG_CORE>("log_core", 1.2037062e-35f, 1024.f, dw, dat, out);
